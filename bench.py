@@ -16,8 +16,8 @@ GPU, config 3 at N=8); each rank runs the fused masking over its clients
 of the uint64 partial sums over xGMI.  `value` is measured on the sharded
 server (every rank receives and decodes its shard of the
 masked sum), its exchange done by ncclReduceScatter in place -- measured
-FIRST, before any other design; the same process group then times every
-other design (`exchange_variants`: the shards also gathered to rank 0, the
+FIRST, before any other design; with --full the same process group then times
+every other design (`exchange_variants`: the shards also gathered to rank 0, the
 sharded server over direct shard transfers, ncclReduce of the partial sums
 to rank 0, element sharding with and without the gather), each contained:
 a design that raises is recorded with its error, one that hangs past
@@ -39,6 +39,18 @@ Inputs: synthetic N(0, 0.01^2) fp32 gradients generated on the GPU
 (torch.Generator seeded 20260116+c); pair seeds (0x5ECA66<<32)|(u<<16)|v as
 in SURVEY.md §8(d).  Generator positions advance by N draws every step
 (a new FL round each step), precomputed before the timed region.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what `value`
+needs and nothing else: it sets up, warms up, times the K steps and prints the
+line.  `--full` adds everything measured or checked beside the headline: the
+CPU baseline (`cpu_baseline`), the same-box draw-loop ceilings behind
+roofline.valu's peaks, the round-0 result check (`check`), and at N > 1 the
+other exchange designs (`exchange_variants`) and the host-resident steps;
+`--extra` (the secondary one-GPU rates) implies it.  `--dump-outputs DIR`
+writes what the headline's last timed step computed as DIR/<name>.npy
+(dump_outputs): the inputs, seeds and stream positions depend only on the
+arguments, so two builds run with the same arguments can be compared output
+for output.
 """
 
 from __future__ import annotations
@@ -114,7 +126,7 @@ def kernel_variant(L: int, X: int, digests: bool) -> int:
 
 # ---------------------------------------------------------------- N > 1 designs
 #
-# Every N > 1 run measures ALL of these in one process group (the headline
+# Every N > 1 run with --full measures ALL of these in one process group (the headline
 # first, with --steps; the rest with --variant-steps), so one driver run of
 # `bench.py --gpus N` reports each exchange design:
 #   sharded          client sharding, every chunk's uint64 partial sum
@@ -188,7 +200,8 @@ def dry_run(args, world: int, rank: int, cpu, wd: Watchdog) -> None:
     line = {"metric": METRIC, "value": r["value"], "dry_run": True, "check": {"round": 0, "decoded_digest": None},
             "data": "dry run: no GPU; every step one gloo all_reduce of 4 KiB (the control flow, not a rate)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
-            "ranks": ranks, "config": {"workload": workload(args, world, head), "design": head.name},
+            "full": args.full, "ranks": ranks,
+            "config": {"workload": workload(args, world, head), "design": head.name},
             "cpu_baseline": cpu, "watchdog_seconds": args.watchdog_seconds,
             "variant_timeout_seconds": args.variant_timeout}
     if multi:
@@ -436,6 +449,34 @@ def settle_check(ctx, r: dict, check_local: int, out: dict, wd: Watchdog) -> Non
         out["exchange_variants"][0]["check_digest"] = x
 
 
+# elements of an output kept by --dump-outputs: <= 2 outputs x (values + positions) x 12 MB
+DUMP_SAMPLE = 1_500_000
+
+
+def dump_outputs(out_dir: str, rank: int, world: int, held: dict) -> None:
+    """--dump-outputs: what the headline's last timed step left on this rank,
+    each device vector as ``<name>.npy`` (``<name>_rank<r>.npy`` at N > 1) in
+    float64: ``masked_sum`` the uint64 masked sum read as signed 64-bit
+    integers (all pair masks cancel in the sum of all clients, leaving the
+    fixed-point sum, |k| < 2^53: exact in float64), ``decoded`` the float64
+    aggregate where the design decodes.  A vector longer than DUMP_SAMPLE is
+    written at DUMP_SAMPLE positions drawn once from a seeded generator (the
+    same positions in every run, sorted), themselves in ``<name>_sample_index``."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, t in held.items():
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20260116)
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+            t = t[idx.to(t.device)]
+            np.save(os.path.join(out_dir, f"{name}_sample_index{sfx}.npy"), idx.numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), t.to(torch.float64).cpu().numpy())
+
+
 def run_design(ctx, v: Variant, steps: int, warmup: int, keep: bool = False) -> dict:
     """Time `steps` steps (after `warmup`) of design `v` on this rank: the
     masking launches on the compute stream, the design's exchange on the
@@ -541,13 +582,23 @@ def run_design(ctx, v: Variant, steps: int, warmup: int, keep: bool = False) -> 
                          device="cpu" if ctx.get("pg_gloo") else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms, xchg_ms = float(t[0]), float(t[1]), float(t[2])
-    try:  # the check is extra: a failure here must not cost the design's timing
-        check = result_check(ctx, v, step, sum_buf, dec, dec_all, sharded, by_elems, e0)
-    except Exception:  # noqa: BLE001
-        import traceback
+    if ctx.get("dump_dir"):  # the headline's last timed step, before the check's step overwrites it
+        held = {}
+        if by_elems or not multi or (not sharded and rank == 0):  # this rank holds (its slice of) the masked sum
+            held["masked_sum"] = sum_buf[:n_loc]
+        if dec_all is not None:
+            held["decoded"] = dec_all[:N]
+        elif dec is not None and (multi or not by_elems):
+            held["decoded"] = dec[:k_el] if by_elems else dec
+        dump_outputs(ctx.pop("dump_dir"), rank, world, held)
+    check = None
+    if args.full:
+        try:  # the check is extra: a failure here must not cost the design's timing
+            check = result_check(ctx, v, step, sum_buf, dec, dec_all, sharded, by_elems, e0)
+        except Exception:  # noqa: BLE001
+            import traceback
 
-        traceback.print_exc()
-        check = None
+            traceback.print_exc()
     flagged = bool(int(flags.item()))
     ms = elapsed * 1e3 / steps
     n_streams = len(plan.pairs) + len(plan.cross)
@@ -662,7 +713,20 @@ def main():
                          "prints the line so far (Watchdog); before it, faulthandler dumps every thread's stack "
                          "and exits 1 (torchrun then stops the other ranks); below the driver's 600 s lease; "
                          "0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the CPU baseline, the same-box "
+                         "draw-loop ceilings (roofline.valu peaks), the round-0 result check, and at N>1 every "
+                         "other exchange design and the host-resident steps; without it a run sets up, warms "
+                         "up, times --steps steps and prints the line (--extra implies --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline's last timed step computed to "
+                         "DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    args.full = args.full or args.extra
+    if not args.full:  # the headline alone; rank processes parse the same command line
+        args.cpu_baseline_seconds = 0.0
+        args.variants = "none"
+        args.host_resident_steps = 0
     if args.variant_steps is None:
         args.variant_steps = max(1, min(200, args.steps))
     for v in (args.variants.split(",") if args.variants not in ("all", "none") else []):
@@ -712,9 +776,9 @@ def rank_main(args):
         dry_run(args, world, rank, cpu, wd)
         return
     multi = world > 1 or args.dist
-    # same-box draw-loop ceilings, also before this process initialises the GPU
+    # same-box draw-loop ceilings (--full), also before this process initialises the GPU
     rehearse = args.rehearse_one_gpu
-    ceil = {} if rehearse else draw_loop_ceilings(local_rank if world > 1 else None)
+    ceil = {} if rehearse or not args.full else draw_loop_ceilings(local_rank if world > 1 else None)
 
     import torch
     import torch.distributed as dist
@@ -768,6 +832,7 @@ def rank_main(args):
            "pg_gloo": multi and dist.get_backend() == "gloo", "names": [f"client{c}" for c in range(C)]}
     head = headline_variant(args, multi)
     wd.enter("headline")
+    ctx["dump_dir"] = args.dump_outputs  # run_design writes the headline's outputs and takes the key out
     r = run_design(ctx, head, args.steps, args.warmup, keep=args.extra and world == 1)
     if r["zero_draw_flag"]:
         print("warning: PRG zero-draw flag raised", file=sys.stderr)
@@ -801,6 +866,7 @@ def rank_main(args):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": r["ms_per_step"],
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -830,7 +896,8 @@ def rank_main(args):
                                               "'dual one7 E2' at 8, median of 15 launches after 40 warm-up"
                                               if len(ceil) == 2 else
                                               "constants from profiles/r01/draw_issue_microbench.txt (another "
-                                              "box): the same-box measurement failed"),
+                                              "box): the same-box measurement " +
+                                              ("failed" if args.full else "runs with --full")),
                               "ideal_ms_per_step": ideal_s * 1e3,
                               "frac": ideal_s / (kern_ms / 1e3),
                               "issue": int_ops}},
@@ -844,7 +911,8 @@ def rank_main(args):
             + "; the N > 1 control flow, not the product's rate")
     out["cpu_baseline"] = cpu
     check_local = r.pop("check_local")
-    out["check"] = {"round": 0, "decoded_digest": None, "note": CHECK_NOTE}
+    out["check"] = {"round": 0, "decoded_digest": None,
+                    "note": CHECK_NOTE if args.full else "the round-0 result check runs with --full"}
     if multi:
         out["designs_agree"] = True
         # the headline is in hand: from here on a failed or hung design (or

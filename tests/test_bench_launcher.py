@@ -34,7 +34,8 @@ def _env():
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_self_launch_spawns_n_ranks_and_prints_one_line(n):
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--cpu-baseline-seconds", "0.2"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--full",
+                        "--cpu-baseline-seconds", "0.2"],
                        capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -55,7 +56,7 @@ def test_outer_torchrun_rank0_measures_cpu_baseline():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
                         "--rdzv-backend", "c10d", "--rdzv-endpoint", "127.0.0.1:0", "--rdzv-id", "outer-test",
                         "--local-addr", "127.0.0.1", BENCH, "--gpus", "2",
-                        "--dry-run", "--cpu-baseline-seconds", "0.2"],
+                        "--dry-run", "--full", "--cpu-baseline-seconds", "0.2"],
                        capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -124,7 +125,7 @@ def test_n_gt_1_line_names_every_exchange_design_and_a_safe_launch():
     driver's 600 s lease."""
     import bench
 
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--cpu-baseline-seconds", "0"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--cpu-baseline-seconds", "0"],
                        capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     (line,) = _json_lines(r.stdout)
@@ -137,7 +138,7 @@ def test_n_gt_1_line_names_every_exchange_design_and_a_safe_launch():
     src = open(os.path.join(ROOT, "benchkit", "launcher.py")).read()
     assert ".bind(" not in src and "--master-port" not in src.split("def launch_ranks")[1].split("def ")[0]
     # a subset, and the headline taken from the flags
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--cpu-baseline-seconds", "0",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--cpu-baseline-seconds", "0",
                         "--exchange", "reduce", "--variants", "elements"],
                        capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -203,8 +204,8 @@ def test_pmc_valu_reads_the_census_of_the_timed_kernel():
 def _dry(n, inject, *extra):
     env = _env()
     env["SFL_BENCH_INJECT"] = inject
-    return subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--cpu-baseline-seconds", "0",
-                           "--steps", "3", "--warmup", "1", *extra],
+    return subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dry-run", "--full",
+                           "--cpu-baseline-seconds", "0", "--steps", "3", "--warmup", "1", *extra],
                           capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
 
 
@@ -380,6 +381,48 @@ def test_position_digest_has_64_live_bits():
     assert (raw(a, i) + raw(b, j) - raw(b, i) - raw(a, j)) % 2**64 == 0
 
 
+def test_plain_run_times_the_headline_alone():
+    """Without --full a run measures nothing beside the headline: no CPU
+    baseline (whatever --cpu-baseline-seconds says) and no other design; the
+    same command with --full brings both back."""
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--dry-run", "--cpu-baseline-seconds", "0.2", "--steps", "2",
+           "--warmup", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = _json_lines(r.stdout)
+    assert line["full"] is False and line["cpu_baseline"] is None and line["steps"] == 2 and line["ms_per_step"] > 0
+    assert [v["name"] for v in line["exchange_variants"]] == ["sharded"]
+    r = subprocess.run(cmd + ["--full"], capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = _json_lines(r.stdout)
+    assert line["full"] is True and line["cpu_baseline"]["value"] > 0 and len(line["exchange_variants"]) > 1
+
+
+def test_dump_outputs_samples_a_long_vector_at_fixed_positions(tmp_path):
+    """--dump-outputs: a vector beyond bench.DUMP_SAMPLE is written at
+    DUMP_SAMPLE seeded positions (sorted, in range, the same in every run)
+    with the positions beside it, a shorter one whole; int64 values come out
+    as the same integers in float64."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n = bench.DUMP_SAMPLE + 12345
+    t = torch.arange(n, dtype=torch.int64) - 7
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, 1, {"masked_sum": t, "decoded": t[:1000].to(torch.float64)})
+    assert sorted(os.listdir(tmp_path / "a")) == ["decoded.npy", "masked_sum.npy", "masked_sum_sample_index.npy"]
+    idx, val = np.load(tmp_path / "a" / "masked_sum_sample_index.npy"), np.load(tmp_path / "a" / "masked_sum.npy")
+    assert idx.dtype == val.dtype == np.float64 and idx.shape == val.shape == (bench.DUMP_SAMPLE,)
+    assert idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) >= 0) and np.array_equal(val, idx - 7)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "masked_sum_sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "decoded.npy"), np.arange(1000.0) - 7)
+    assert 2 * (idx.nbytes + val.nbytes + 256) <= 64 << 20  # two outputs with their positions: within 64 MB
+    bench.dump_outputs(str(tmp_path / "c"), 3, 8, {"decoded": t[:10].to(torch.float64)})
+    assert os.listdir(tmp_path / "c") == ["decoded_rank3.npy"]
+
+
 def test_importing_the_bench_loads_no_torch():
     """The self-launcher process must not touch the GPU before it starts its
     rank processes (nothing may be exec'd from a process that initialised
@@ -411,7 +454,7 @@ def test_dry_run_n8_line_carries_the_exchange_model():
     is link- or kernel-bound -- roofline.exchange with the bytes per link,
     the assumed per-link peak and its source, and the predicted step from
     the rank's kernel time (--dry-run: the committed per-rank kernel time)."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run", "--cpu-baseline-seconds", "0",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run", "--full", "--cpu-baseline-seconds", "0",
                         "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=240, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -114,7 +114,7 @@ def test_bench_n_ranks_every_design(world, comm, check_1m):
     env = rehearsal_env(dict(os.environ))
     t0, before = time.time(), host_counters()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu",
-                        "--rehearse-comm", comm,
+                        "--rehearse-comm", comm, "--full",
                         "--elems", "1000003", "--steps", "3", "--warmup", "1", "--variant-steps", "2",
                         "--host-resident-steps", "3", "--cpu-baseline-seconds", "0", "--watchdog-seconds", "150"],
                        capture_output=True, text=True, timeout=170, env=env, cwd=ROOT)
@@ -179,7 +179,7 @@ def test_bench_n1_line(check_1m):
     if not has_gpu():
         pytest.skip("no GPU")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--elems", "1000003", "--steps", "5",
-                        "--warmup", "2", "--cpu-baseline-seconds", "0"],
+                        "--warmup", "2", "--full", "--cpu-baseline-seconds", "0"],
                        capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
@@ -193,6 +193,29 @@ def test_bench_n1_line(check_1m):
     assert 0 < rf["kernel_ms_per_step"] <= d["ms_per_step"] * 1.01
     assert abs(d["value"] - 8 * 1000003 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
     assert d["check"]["decoded_digest"] == check_1m
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(check_1m, tmp_path):
+    """The driver's plain form (no --full): the headline alone -- no CPU
+    baseline, no result check, the draw-loop peaks from the committed
+    constants -- and --dump-outputs writes the last timed step's masked sum:
+    the pair masks cancel in it whatever the step's stream positions, so it
+    decodes to the oracle's round-0 aggregate."""
+    if not has_gpu():
+        pytest.skip("no GPU")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--elems", "1000003",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    (d,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and d["check"]["decoded_digest"] is None and "extra" not in d
+    assert "--full" in d["roofline"]["valu"]["peak_source"]
+    assert abs(d["value"] - 8 * 1000003 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["masked_sum.npy"]
+    s = np.load(tmp_path / "out" / "masked_sum.npy")
+    assert s.dtype == np.float64 and s.shape == (1000003,)
+    assert f"{digest_np(s / 2.0**18):016x}" == check_1m
 
 
 def host_counters() -> dict:
@@ -248,7 +271,7 @@ def _rehearse(world, inject, *extra, timeout=170):
     env["SFL_BENCH_INJECT"] = inject
     t0, before = time.time(), host_counters()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu",
-                           "--elems", "1000003", "--steps", "3", "--warmup", "1", "--variant-steps", "2",
+                           "--elems", "1000003", "--steps", "3", "--warmup", "1", "--full", "--variant-steps", "2",
                            "--host-resident-steps", "0", "--cpu-baseline-seconds", "0", "--watchdog-seconds", "150",
                            *extra],
                           capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
@@ -295,7 +318,8 @@ def _full_size_line(*extra, timeout=150):
     env = rehearsal_env(dict(os.environ))
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0",
-                        "--cpu-baseline-seconds", "0", "--variants", "none", "--host-resident-steps", "0", *extra],
+                        "--full", "--cpu-baseline-seconds", "0", "--variants", "none", "--host-resident-steps", "0",
+                        *extra],
                        capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     _keep_stderr("full_size" + ("_w8" if "--gpus" in extra else "_n1"), r, t0, slow=40.0)
     assert r.returncode == 0, _explain(r)

@@ -231,7 +231,7 @@ def test_bench_self_launched_dist_world1(opts):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--elems",
-                        "1000003", "--steps", "3", "--warmup", "1", "--variant-steps", "2",
+                        "1000003", "--steps", "3", "--warmup", "1", "--full", "--variant-steps", "2",
                         "--cpu-baseline-seconds", "0", "--watchdog-seconds", "100", *opts],
                        capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
