@@ -65,6 +65,35 @@ def gauss(key: int, counter0: int, n: int) -> np.ndarray:
     return z.reshape(-1)[off:off + n]
 
 
+def philox_words(key: int, counter0: int, n: int) -> np.ndarray:
+    """The (blocks, 4) uint32 Philox words behind elements counter0 ..
+    counter0+n-1: row b is counter block counter0 // 4 + b (the words
+    ``gauss`` forms)."""
+    b0, b1 = counter0 // 4, (counter0 + n + 3) // 4
+    blk = np.arange(b0, b1, dtype=np.uint64)
+    ctr = np.zeros((blk.size, 4), dtype=np.uint32)
+    ctr[:, 0] = (blk & MASK32).astype(np.uint32)
+    ctr[:, 1] = (blk >> np.uint64(32)).astype(np.uint32)
+    return philox4x32_10(ctr, (key & 0xFFFFFFFF, key >> 32))
+
+
+def gauss64(key: int, counter0: int, n: int) -> np.ndarray:
+    """``gauss`` with every step in float64 -- the high-precision reference
+    of the normals: u1 = ((w >> 8) + 1) 2^-24, u2 = (w >> 8) 2^-24 (both exact),
+    rad = sqrt(-2 ln u1), z = rad cos(2 pi u2), rad sin(2 pi u2).  Same element
+    layout: element e is normal e & 3 of block e >> 2."""
+    r = philox_words(key, counter0, n)
+    z = np.empty((r.shape[0], 4), dtype=np.float64)
+    for j in range(2):
+        u1 = ((r[:, 2 * j] >> 8).astype(np.float64) + 1.0) * 2.0**-24
+        u2 = (r[:, 2 * j + 1] >> 8).astype(np.float64) * 2.0**-24
+        rad = np.sqrt(-2.0 * np.log(u1))
+        z[:, 2 * j] = rad * np.cos(2.0 * np.pi * u2)
+        z[:, 2 * j + 1] = rad * np.sin(2.0 * np.pi * u2)
+    off = counter0 - (counter0 // 4) * 4
+    return z.reshape(-1)[off:off + n]
+
+
 def layer_norm32(a) -> np.float32:
     """``np.linalg.norm(a)`` of a float32 array (numpy 1.23.5: ``sqrt(x.dot(x))``
     in float32) -- the dot here the exact float64 sum rounded once (the
