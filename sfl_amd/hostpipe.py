@@ -23,6 +23,10 @@ MI355X: ~57 GB/s each way, ~79 GB/s both ways at once), not the kernels (a
   drain thread copies it into a fresh ``np.empty`` (faulting its pages on
   the pool's threads) while chunk j+1 is in flight.
 
+``run_chunks`` is the one place that wires these together (events, the
+chunk loop, the order in which everything is drained and unregistered);
+its callers supply their device buffers and per-chunk launches.
+
 Nothing here computes: the kernels are the library's (``sa_mask``,
 ``sa_xor_u64``, ``sa_sum_u64``, ``sa_decode``, ``sa_fused_clients``).  Used
 by ``security/aggregation/party.py`` and ``secure_aggregator.py``.
@@ -688,3 +692,63 @@ class Phases:
                 t = tm
             print(f"[hostpipe] {self.what}: " + ", ".join(parts) + f" | total {1e3 * (t - self.t0):.2f} ms",
                   file=sys.stderr, flush=True)
+
+
+def run_chunks(what: str, dev, bounds, inputs, out_dtype, setup, *, register: bool = True):
+    """One pipelined call: the skeleton every chunked host path shares.
+    ``bounds`` cut [0, n) into chunks; ``inputs`` are the host arrays to
+    register for the call (``Pinned``).  ``setup()`` runs once on ``dev``'s
+    current stream, inside the registration: it allocates the caller's
+    device buffers and returns
+
+    * ``copies``: chunk j's H2D copies, as ``Feeder`` / ``Issued`` take them;
+    * ``compute(j, lo, hi)``: chunk j's device work, run under the compute
+      stream once chunk j's copies are ordered before it;
+    * ``result_of(j)``: the device slice of chunk j's result, for its D2H;
+    * ``meta``: a small device tensor read back after the last chunk, or None.
+
+    Returns (host result of n ``out_dtype`` elements, meta as a numpy array
+    or None).  On any error the streams are drained before the inputs are
+    unregistered, both helper threads are joined, and the error is raised."""
+    import torch
+
+    ph = Phases(what)
+    out = FreshOutput(bounds[-1][1] if bounds else 0, out_dtype, bounds)  # its pages start faulting in now
+    s_in, s_k, s_out = streams(dev)
+    meta_h = None
+    with torch.cuda.device(dev), Pinned(inputs, register=register) as pin:
+        ph.mark("register in")
+        cur = torch.cuda.current_stream(dev)
+        copies, compute, result_of, meta = setup()
+        ready = torch.cuda.Event()  # the caller's buffers exist (and are zeroed) from here on
+        ready.record(cur)
+        s_in.wait_event(ready)
+        s_k.wait_event(ready)
+        # registered inputs: async DMA issued from this thread; else staged by the feeder
+        feed = Issued(s_in, copies, pin) if pin.ok else Feeder(s_in, copies)
+        try:
+            for j, (lo, hi) in enumerate(bounds):  # chunk j launches once its copies in are issued
+                e_in, e_k = feed.ready(j), torch.cuda.Event()
+                with torch.cuda.stream(s_k):
+                    s_k.wait_event(e_in)
+                    compute(j, lo, hi)
+                    e_k.record(s_k)
+                out.copy_in(j, result_of(j), s_out, e_k)
+            if meta is not None:
+                meta_h = torch.empty(meta.numel(), dtype=meta.dtype, pin_memory=True)
+                with torch.cuda.stream(s_k):
+                    meta_h.copy_(meta, non_blocking=True)
+            ph.mark("pipeline")
+        finally:
+            feed.join(check=False)  # the feeder is done with the inputs
+            out.close()
+            s_k.synchronize()
+            s_out.synchronize()
+            s_in.synchronize()
+            cur.wait_stream(s_k)  # the caller's buffers were allocated on the current stream
+        feed.join()
+        ph.mark("wait")
+    ph.mark("unregister")
+    ph.note(pinned=pin.ok, **pin.stats, **out.stats)
+    ph.done()
+    return out.array, None if meta_h is None else meta_h.numpy()

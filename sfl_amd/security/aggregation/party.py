@@ -28,6 +28,7 @@ spawned process per party.
 
 from __future__ import annotations
 
+import functools
 import os
 import threading
 from dataclasses import dataclass, field
@@ -37,6 +38,14 @@ import numpy as np
 from .masker import Masker
 
 _F32, _F64, _I64 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def _torch_dtypes() -> dict:
+    """The three element / arithmetic types as torch dtypes (torch is imported on first use)."""
+    import torch
+
+    return {_F32: torch.float32, _F64: torch.float64, _I64: torch.int64}
 
 
 # the server's large sum_decode stages vectors that are not pooled results
@@ -249,7 +258,7 @@ def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, 
     if gpu is None:
         raise RuntimeError("the party has no GPU: libsfl_sa masks on the device")
     dev = torch.device("cuda", gpu)
-    tdt = {_F32: torch.float32, _F64: torch.float64, _I64: torch.int64}
+    tdt = _torch_dtypes()
     n = int(sum(int(np.prod(_shape_of(a))) for a in xs))
     small = 8 * n <= SMALL_CALL_BYTES
     streams = masker.streams()
@@ -351,62 +360,29 @@ def _mask_vector_pipelined(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype,
     from ... import kernels as K
 
     dev = torch.device("cuda", gpu)
-    tdt = {_F32: torch.float32, _F64: torch.float64, _I64: torch.int64}
-    ph = H.Phases("mask_payload")
+    tdt = _torch_dtypes()
     layers = H.host_layers(xs, xt)
     n = int(sum(a.size for a in layers))
     bounds = H.page_bounds(H.chunk_bounds(n, target=16), [layers])
-    out = H.FreshOutput(n, np.uint64, bounds)  # its pages start faulting in now
-    s_in, s_k, s_out = H.streams(dev)
-    with torch.cuda.device(dev), H.Pinned(layers) as pin:
-        cur = torch.cuda.current_stream(dev)
+
+    def setup():
         x = torch.empty(n, dtype=tdt[xt], device=dev)
         buf = torch.empty(n + 2, dtype=K.U64, device=dev)  # masked vector | digest | flag word
         res, dig, flags = buf[:n], buf[n:n + 1], buf[n + 1:].view(torch.int32)[:1]
         buf[n:].zero_()
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        s_in.wait_event(ready)
-        s_k.wait_event(ready)
+
+        def compute(j, lo, hi):
+            K.mask(x[lo:hi], res[lo:hi], masker.streams(offset=lo), weight=wscalar,
+                   compute_dtype=tdt[ct], fxp_bits=masker.fxp_bits, digest=dig, flags=flags)
+
         copies = [[(x[lo:hi], H.pieces(layers, lo, hi))] for lo, hi in bounds]
-        # registered layers: every H2D issued at once, async; else staged by the feeder
-        feed = H.Issued(s_in, copies, pin) if pin.ok else H.Feeder(s_in, copies)
-        try:
-            def launch(j):
-                lo, hi = bounds[j]
-                e_k = torch.cuda.Event()
-                with torch.cuda.stream(s_k):
-                    s_k.wait_event(feed.ready(j))
-                    K.mask(x[lo:hi], res[lo:hi], masker.streams(offset=lo), weight=wscalar,
-                           compute_dtype=tdt[ct], fxp_bits=masker.fxp_bits, digest=dig, flags=flags)
-                    e_k.record(s_k)
-                return e_k
+        return copies, compute, lambda j: res[bounds[j][0]:bounds[j][1]], buf[n:]
 
-            def d2h(j, e_k):
-                lo, hi = bounds[j]
-                out.copy_in(j, res[lo:hi], s_out, e_k)
-
-            for j in range(len(bounds)):  # chunk j launches once the feeder has issued its copy in
-                d2h(j, launch(j))
-            meta = torch.empty(2, dtype=K.U64, pin_memory=True)
-            with torch.cuda.stream(s_k):
-                meta.copy_(buf[n:], non_blocking=True)
-            ph.mark("pipeline")
-        finally:
-            feed.join(check=False)  # the feeder is done with the inputs
-            out.close()
-            s_k.synchronize()
-            s_out.synchronize()
-            s_in.synchronize()
-            cur.wait_stream(s_k)  # x / buf were allocated on the current stream
-        feed.join()
-        ph.mark("wait")
-    ph.note(pinned=pin.ok, **pin.stats, **out.stats)
-    ph.done()
+    out, meta = H.run_chunks("mask_payload", dev, bounds, layers, np.uint64, setup)
     digest, flag = int(meta[0]) & ((1 << 64) - 1), int(meta[1]) & 0xFFFFFFFF
     if flag & L.SA_FLAG_PRG_REJECT:
         return None
-    return out.array, {}, digest
+    return out, {}, digest
 
 
 def _shape_of(a):
@@ -457,6 +433,13 @@ class DigestMismatch(RuntimeError):
     """A masked vector changed between the client and the server."""
 
 
+def _check_digests(got, digests) -> None:
+    """``got``: the XOR digests the server formed, vector by vector, against the ones sent."""
+    for i, (g, want) in enumerate(zip(got, digests)):
+        if int(g) != int(want) & ((1 << 64) - 1):
+            raise DigestMismatch(f"masked vector {i}: digest {int(g):016x}, sent {int(want):016x}")
+
+
 def _sum_decode_vectors(u64s, digests, fxp_bits, divisor, divisor_vec, gpu, as_torch):
     """The server's device work: the payloads in (one pinned copy for a small
     call), their XOR digests, the mod-2^64 sum and the decode; the decoded
@@ -478,9 +461,7 @@ def _sum_decode_vectors(u64s, digests, fxp_bits, divisor, divisor_vec, gpu, as_t
         with _SCRATCH_LOCK, torch.cuda.device(dev):
             pin, dbuf = _scratch(gpu, *K.sum_decode_host_scratch(C, n))
             result, got = K.sum_decode_host(u64s, pin, dbuf, fxp_bits=fxp_bits, divisor=divisor)
-        for i, (g, want) in enumerate(zip(got.tolist(), digests)):
-            if int(g) != int(want) & ((1 << 64) - 1):
-                raise DigestMismatch(f"masked vector {i}: digest {int(g):016x}, sent {int(want):016x}")
+        _check_digests(got.tolist(), digests)
         return result
     if not small and not as_torch and divisor_vec is None and LARGE_PIPELINE:
         return _sum_decode_pipelined(u64s, digests, fxp_bits, divisor, dev)
@@ -519,9 +500,7 @@ def _sum_decode_vectors(u64s, digests, fxp_bits, divisor, divisor_vec, gpu, as_t
             else:
                 got = K.as_u64(dig).tolist()
                 result = out if as_torch else H.d2h(out)
-            for i, (g, want) in enumerate(zip(got, digests)):
-                if int(g) != int(want) & ((1 << 64) - 1):
-                    raise DigestMismatch(f"masked vector {i}: digest {int(g):016x}, sent {int(want):016x}")
+            _check_digests(got, digests)
             return result
     return out if as_torch else H.d2h(out)
 
@@ -541,56 +520,29 @@ def _sum_decode_pipelined(u64s, digests, fxp_bits, divisor, dev):
     from ... import kernels as K
 
     C, n = len(u64s), int(u64s[0].size)
-    ph = H.Phases("sum_decode")
     ins = [np.ascontiguousarray(u).reshape(-1).view(np.int64) for u in u64s]
     bounds = H.chunk_bounds(n)
-    out = H.FreshOutput(n, np.float64, bounds)
-    s_in, s_k, s_out = H.streams(dev)
-    # vectors received from parties in this process sit in pooled (registered)
-    # results: copied async as they are; anything else (vectors deserialised
-    # from another process) is staged by the feeder (or, SERVER_REGISTER,
-    # registered lazily as its copies are reached)
-    with torch.cuda.device(dev), H.Pinned(ins, register=SERVER_REGISTER) as pin:
-        cur = torch.cuda.current_stream(dev)
+
+    def setup():
         vecs = [torch.empty(n, dtype=K.U64, device=dev) for _ in range(C)]
         s = torch.empty(n, dtype=K.U64, device=dev)
         dec = torch.empty(n, dtype=torch.float64, device=dev)
         dig = torch.zeros(C, dtype=K.U64, device=dev)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        s_in.wait_event(ready)
-        s_k.wait_event(ready)
+
+        def compute(j, lo, hi):
+            part = [v[lo:hi] for v in vecs]
+            for i, v in enumerate(part):
+                K.xor_digest(v, dig[i:i + 1])
+            K.sum_u64(part, s[lo:hi])
+            K.decode(s[lo:hi], dec[lo:hi], fxp_bits=fxp_bits, divisor=divisor)
 
         copies = [[(v[lo:hi], [(h[lo:hi], 0)]) for v, h in zip(vecs, ins)] for lo, hi in bounds]
-        feed = H.Issued(s_in, copies, pin) if pin.ok else H.Feeder(s_in, copies)
-        try:
-            for j, (lo, hi) in enumerate(bounds):
-                e_in, e_k = feed.ready(j), torch.cuda.Event()
-                with torch.cuda.stream(s_k):
-                    s_k.wait_event(e_in)
-                    part = [v[lo:hi] for v in vecs]
-                    for i, v in enumerate(part):
-                        K.xor_digest(v, dig[i:i + 1])
-                    K.sum_u64(part, s[lo:hi])
-                    K.decode(s[lo:hi], dec[lo:hi], fxp_bits=fxp_bits, divisor=divisor)
-                    e_k.record(s_k)
-                out.copy_in(j, dec[lo:hi], s_out, e_k)
-            got_h = torch.empty(C, dtype=K.U64, pin_memory=True)
-            with torch.cuda.stream(s_k):
-                got_h.copy_(dig, non_blocking=True)
-            ph.mark("pipeline")
-        finally:
-            feed.join(check=False)  # the feeder is done with the inputs
-            out.close()
-            s_k.synchronize()
-            s_out.synchronize()
-            s_in.synchronize()
-            cur.wait_stream(s_k)
-        feed.join()
-        ph.mark("wait")
-    ph.note(pinned=pin.ok, **pin.stats, **out.stats)
-    ph.done()
-    for i, (g, want) in enumerate(zip(got_h.numpy().view(np.uint64).tolist(), digests)):
-        if int(g) != int(want) & ((1 << 64) - 1):
-            raise DigestMismatch(f"masked vector {i}: digest {int(g):016x}, sent {int(want):016x}")
-    return out.array
+        return copies, compute, lambda j: dec[bounds[j][0]:bounds[j][1]], dig
+
+    # vectors received from parties in this process sit in pooled (registered)
+    # results: copied async as they are; anything else (vectors deserialised
+    # from another process) is staged by the feeder (or, SERVER_REGISTER,
+    # registered lazily as its copies are reached)
+    out, got = H.run_chunks("sum_decode", dev, bounds, ins, np.float64, setup, register=SERVER_REGISTER)
+    _check_digests(got.view(np.uint64).tolist(), digests)
+    return out

@@ -32,6 +32,7 @@ take go through the general path above.
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List
 
 import numpy as np
@@ -98,6 +99,49 @@ def _compute_dtype(ldt: np.dtype, w, fxp_bits: int) -> np.dtype:
     return (probe * (1 << fxp_bits)).dtype
 
 
+@dataclass
+class _Call:
+    """One aggregation call as the host paths see it: the parties' objects
+    and names, their layers (same sizes and shapes for every party), the
+    host weights, and how the result goes back (``is_list`` / ``container``:
+    the payloads' own kind).  ``C`` parties, ``n`` elements a party."""
+    server: PYU
+    data: list
+    names: list
+    layer_lists: tuple
+    sizes: list
+    shapes: list
+    weights: list | None
+    average: bool
+    is_list: bool
+    container: str  # "array" | "list" | "tuple", as party.MaskedPayload names them
+    C: int
+    n: int
+
+    def divisor(self) -> float:
+        """What the decoded sum is divided by under scalar weights: 1, C or sum(weights)."""
+        if not self.average:
+            return 1.0
+        return float(self.C) if self.weights is None else float(sum(self.weights))
+
+    def scalar_weights(self, kind: str = "f") -> list:
+        """Every party's scalar weight in the arithmetic's kind (float, or "i": int)."""
+        if self.weights is None:
+            return [1.0] * self.C
+        return [float(w) if kind == "f" else int(w) for w in self.weights]
+
+    def pack(self, layers: list) -> PYUObject:
+        """The per-layer results in the payloads' container, on the server."""
+        if not self.is_list:
+            return PYUObject(self.server, layers[0])
+        return PYUObject(self.server, tuple(layers) if self.container == "tuple" else layers)
+
+    def wrap(self, flat: np.ndarray) -> PYUObject:
+        """A flat host result split into the layers' shapes, packed."""
+        parts = np.split(flat, np.cumsum(self.sizes)[:-1]) if len(self.sizes) > 1 else [flat]
+        return self.pack([p.reshape(sh) for p, sh in zip(parts, self.shapes)])
+
+
 class SecureAggregator(Aggregator):
     """Pairwise-mask secure aggregation with the HIP hot path.
 
@@ -132,6 +176,7 @@ class SecureAggregator(Aggregator):
         self.last_masked = None
         self.last_digests = None
         self._careful = False  # replay mode after a flagged rejection (see _aggregate)
+        self._scratch = {}  # the one-call library entries' buffers (_call_scratch)
         self._maskers = {n: Masker(n, self._fxp_bits) for n in names}
         if seeds is None:
             keys = {n: m.public_key for n, m in self._maskers.items()}
@@ -240,12 +285,13 @@ class SecureAggregator(Aggregator):
         # layers are masked in order with one stream position per (party, peer),
         # exactly like the reference's per-layer rng.integers calls
         sizes = [int(np.prod(sh)) if sh else 1 for sh in shapes]
-        if self._host_fusable(data, layer_lists, as_torch, weights, sum(sizes)):
-            return self._aggregate_host_fused(data, layer_lists, sizes, shapes, weights, average, is_list,
-                                              payloads, digests_keep)
+        container = "tuple" if isinstance(payloads[0], tuple) else ("list" if is_list else "array")
+        call = _Call(server, data, owners, layer_lists, sizes, shapes, weights, average, is_list, container,
+                     len(data), sum(sizes))
+        if self._host_fusable(data, layer_lists, as_torch, weights, call.n):
+            return self._aggregate_host_fused(call)
         if not as_torch:
-            res = self._host_general_one_call(data, layer_lists, sizes, shapes, weights, average, is_list,
-                                              payloads, digests_keep)
+            res = self._host_general_one_call(call)
             if res is not None:
                 return res
         flags = torch.zeros(1, dtype=torch.int32, device=sdev)
@@ -254,8 +300,7 @@ class SecureAggregator(Aggregator):
             # host payloads of one dtype: pack on the host, one H2D copy per party
             flat = [np.concatenate([np.asarray(a).reshape(-1) for a in ll]) for ll in layer_lists]
             g = self._prepare_layer(data, flat, (sum(sizes),), weights)
-            return self._finish(data, [(list(range(nl)), sizes, g)], shapes, weights, average, as_torch,
-                                is_list, payloads, flags, masked_keep, digests_keep)
+            return self._finish(call, [(list(range(nl)), sizes, g)], as_torch, flags, masked_keep, digests_keep)
         prepared = [self._prepare_layer(data, [ll[li] for ll in layer_lists], shapes[li], weights)
                     for li in range(nl)]
         # Consecutive layers draw consecutive stream positions, so when every
@@ -275,8 +320,7 @@ class SecureAggregator(Aggregator):
         else:
             groups = [([li], [prepared[li]["n"]], prepared[li]) for li in range(nl)]
 
-        return self._finish(data, groups, shapes, weights, average, as_torch, is_list, payloads, flags,
-                            masked_keep, digests_keep)
+        return self._finish(call, groups, as_torch, flags, masked_keep, digests_keep)
 
     # ------------------------------------------- host payloads, one launch
     def _host_fusable(self, data, layer_lists, as_torch, weights, n) -> bool:
@@ -324,8 +368,32 @@ class SecureAggregator(Aggregator):
             self._stage = st
         return st
 
-    def _aggregate_host_fused(self, data, layer_lists, sizes, shapes, weights, average, is_list, payloads,
-                              digests_keep):
+    def _accept(self, call: _Call, flag: int, digests) -> None:
+        """The end of a host path's round.  A set PRG flag rejects it before
+        any stream has moved (the replay starts from the same positions);
+        else every party's streams move on by n and ``digests`` (the one
+        launch group's, or None) become ``last_digests``."""
+        if flag & L.SA_FLAG_PRG_REJECT:
+            raise _Rejected()
+        for nm in call.names:
+            self._maskers[nm].consume(call.n)
+        self.last_digests = [digests]
+
+    def _call_scratch(self, sizes, *args):
+        """(pinned, device) scratch of a blocking one-call library entry,
+        sized by ``sizes(*args)`` (``kernels.host_fused_scratch`` /
+        ``host_clients_scratch``) and kept per entry until its shape changes."""
+        sdev = self._device.torch_device
+        key = (*args, str(sdev))
+        sc = self._scratch.get(sizes)
+        if sc is None or sc[0] != key:
+            pin_b, dev_b = sizes(*args)
+            sc = (key, torch.empty(pin_b, dtype=torch.uint8, pin_memory=True),
+                  torch.empty(dev_b, dtype=torch.uint8, device=sdev))
+            self._scratch[sizes] = sc
+        return sc[1], sc[2]
+
+    def _aggregate_host_fused(self, call: _Call):
         """Small calls (up to SMALL_CALL_BYTES a party): ONE blocking library
         call (``_host_one_call``: the parties' layers packed into one pinned
         block, one H2D copy, one zero fill of the PRG flag + digests, the
@@ -336,25 +404,24 @@ class SecureAggregator(Aggregator):
         need the general machinery.  Large calls copy each party's array and
         the result directly."""
         sdev = self._device.torch_device
-        C, n = len(data), sum(sizes)
+        C, n = call.C, call.n
         n_pad = -(-n // 4) * 4  # rows start 16-byte aligned
         # small calls: one pinned block, one copy; large ones: the driver's
         # pageable copy per party (its staging pipelines, a host memcpy into
         # pinned memory first does not)
         big = 4 * n_pad > SMALL_CALL_BYTES
         if big and not self._careful and P.LARGE_PIPELINE:
-            return self._host_fused_pipelined(data, layer_lists, sizes, shapes, weights, average, is_list,
-                                              payloads, digests_keep, C, n, sdev)
+            return self._host_fused_pipelined(call)
         if not big and not self._careful and C <= MAX_FUSED_CLIENTS:
-            res = self._host_one_call(data, layer_lists, sizes, shapes, weights, average, is_list, payloads,
-                                      digests_keep, C, n, sdev)
+            res = self._host_one_call(call)
             if res is not None:
                 return res
         st = self._staging(C, n_pad, sdev)
         host = st["in_np"]
+        digests_keep = []
         with torch.cuda.device(sdev):
             dev_in = st["in_dev"]
-            for c, ll in enumerate(layer_lists):
+            for c, ll in enumerate(call.layer_lists):
                 if big:
                     src = (np.asarray(ll[0], dtype=np.float32).reshape(-1) if len(ll) == 1 else
                            np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in ll]))
@@ -367,13 +434,9 @@ class SecureAggregator(Aggregator):
                 dev_in.copy_(st["in_host"], non_blocking=True)
             st["meta"].zero_()
             xs = [dev_in[c, :n] for c in range(C)]
-            ws = [1.0 if weights is None else float(w) for w in (weights or [None] * C)]
-            s = self._masked_sum(data, xs, [np.dtype(np.float32)] * C, ws, [None] * C, n, st["flags"], [],
-                                 digests_keep, s_out=st["sum"][:n], digests_out=st["digests"])
-            divisor = 1.0
-            if average:
-                divisor = float(C) if weights is None else float(sum(weights))
-            K.decode(s, st["io_dev"][:n], fxp_bits=self._fxp_bits, divisor=divisor)
+            s = self._masked_sum(call.data, xs, [np.dtype(np.float32)] * C, call.scalar_weights(), [None] * C, n,
+                                 st["flags"], [], digests_keep, s_out=st["sum"][:n], digests_out=st["digests"])
+            K.decode(s, st["io_dev"][:n], fxp_bits=self._fxp_bits, divisor=call.divisor())
             if big:
                 out = H.d2h(st["io_dev"][:n])
                 st["io_host"][n_pad:].copy_(st["io_dev"][n_pad:])
@@ -387,14 +450,9 @@ class SecureAggregator(Aggregator):
             raise _Rejected()
         self.last_digests = [None if d is None else torch.from_numpy(ioi[n_pad + 1:n_pad + 1 + C].copy())
                              for d in digests_keep]
-        parts = np.split(out, np.cumsum(sizes)[:-1]) if len(sizes) > 1 else [out]
-        result = [p.reshape(sh) for p, sh in zip(parts, shapes)]
-        if not is_list:
-            return PYUObject(self._device, result[0])
-        return PYUObject(self._device, tuple(result) if isinstance(payloads[0], tuple) else result)
+        return call.wrap(out)
 
-    def _host_fused_pipelined(self, data, layer_lists, sizes, shapes, weights, average, is_list, payloads,
-                              digests_keep, C, n, sdev):
+    def _host_fused_pipelined(self, call: _Call):
         """Large host float32 payloads of co-located parties, chunked
         through three streams (``sfl_amd/hostpipe.py``, as the per-party
         drop-in's large path): chunk j of every party's layers H2D straight
@@ -406,23 +464,15 @@ class SecureAggregator(Aggregator):
         reached through a pinned slot).  Bit-identical to one fused launch over
         [0, n); more than 8 parties take the pair-shared schedule per chunk
         (``kernels.fused_many``: the sum only, no per-party digests)."""
-        from ... import hostpipe as H
-
-        ph = H.Phases("average" if average else "sum")
-        names = [d.device.party for d in data]
-        pair_gens, pair_signs = self._pair_streams(names)
-        ws = [1.0 if weights is None else float(w) for w in (weights or [None] * C)]
-        divisor = 1.0
-        if average:
-            divisor = float(C) if weights is None else float(sum(weights))
-        layers = [H.host_layers(ll, np.float32) for ll in layer_lists]
+        sdev = self._device.torch_device
+        C, n = call.C, call.n
+        pair_gens, pair_signs = self._pair_streams(call.names)
+        ws, divisor = call.scalar_weights(), call.divisor()
+        layers = [H.host_layers(ll, np.float32) for ll in call.layer_lists]
         n_pad = -(-n // 4) * 4  # rows 16-byte aligned
         bounds = H.page_bounds(H.chunk_bounds(n), layers)
-        out = H.FreshOutput(n, np.float64, bounds)  # its pages start faulting in now
-        s_in, s_k, s_out = H.streams(sdev)
-        with torch.cuda.device(sdev), H.Pinned([a for ls in layers for a in ls]) as pin:
-            ph.mark("register in")
-            cur = torch.cuda.current_stream(sdev)
+
+        def setup():
             x = torch.empty((C, n_pad), dtype=torch.float32, device=sdev)
             ssum = torch.empty(n, dtype=K.U64, device=sdev)
             dec = torch.empty(n, dtype=torch.float64, device=sdev)
@@ -430,54 +480,21 @@ class SecureAggregator(Aggregator):
             # more parties than one launch holds: the pair-shared schedule
             # (kernels.fused_many) forms only the sum, no per-party digests
             flags, digests = meta[:1].view(torch.int32)[:1], (meta[1:] if C <= MAX_FUSED_CLIENTS else None)
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            s_in.wait_event(ready)
-            s_k.wait_event(ready)
+
+            def compute(j, lo, hi):
+                gens = L.pcg64_advance_many(pair_gens, [lo] * len(pair_gens)) if lo else pair_gens
+                K.fused_clients([x[c, lo:hi] for c in range(C)], ws, gens, pair_signs, [], 0, ssum[lo:hi],
+                                fxp_bits=self._fxp_bits, digests=digests, flags=flags)
+                K.decode(ssum[lo:hi], dec[lo:hi], fxp_bits=self._fxp_bits, divisor=divisor)
 
             copies = [[(x[c, lo:hi], H.pieces(layers[c], lo, hi)) for c in range(C)] for lo, hi in bounds]
-            # registered layers: every H2D issued at once, async; else staged by the feeder
-            feed = H.Issued(s_in, copies, pin) if pin.ok else H.Feeder(s_in, copies)
-            try:
-                for j, (lo, hi) in enumerate(bounds):
-                    gens = L.pcg64_advance_many(pair_gens, [lo] * len(pair_gens)) if lo else pair_gens
-                    e_in, e_k = feed.ready(j), torch.cuda.Event()
-                    with torch.cuda.stream(s_k):
-                        s_k.wait_event(e_in)
-                        K.fused_clients([x[c, lo:hi] for c in range(C)], ws, gens, pair_signs, [], 0, ssum[lo:hi],
-                                        fxp_bits=self._fxp_bits, digests=digests, flags=flags)
-                        K.decode(ssum[lo:hi], dec[lo:hi], fxp_bits=self._fxp_bits, divisor=divisor)
-                        e_k.record(s_k)
-                    out.copy_in(j, dec[lo:hi], s_out, e_k)
-                meta_h = torch.empty(1 + C, dtype=K.U64, pin_memory=True)
-                with torch.cuda.stream(s_k):
-                    meta_h.copy_(meta, non_blocking=True)
-                ph.mark("pipeline")
-            finally:
-                feed.join(check=False)  # the feeder is done with the inputs
-                out.close()
-                s_k.synchronize()
-                s_out.synchronize()
-                s_in.synchronize()
-                cur.wait_stream(s_k)  # x, ssum, dec, meta were allocated on the current stream
-            feed.join()
-            ph.mark("wait")
-        ph.mark("unregister")
-        ph.note(pinned=pin.ok, **pin.stats, **out.stats)
-        ph.done()
-        mh = meta_h.numpy()
-        if int(mh[0]) & L.SA_FLAG_PRG_REJECT:  # the flag word's low half (little-endian)
-            raise _Rejected()
-        for nm in names:
-            self._maskers[nm].consume(n)
-        digests_keep.append(torch.from_numpy(mh[1:].copy()) if C <= MAX_FUSED_CLIENTS else None)
-        self.last_digests = digests_keep
-        res = out.array
-        parts = np.split(res, np.cumsum(sizes)[:-1]) if len(sizes) > 1 else [res]
-        result = [p.reshape(sh) for p, sh in zip(parts, shapes)]
-        if not is_list:
-            return PYUObject(self._device, result[0])
-        return PYUObject(self._device, tuple(result) if isinstance(payloads[0], tuple) else result)
+            return copies, compute, lambda j: dec[bounds[j][0]:bounds[j][1]], meta
+
+        out, mh = H.run_chunks("average" if call.average else "sum", sdev, bounds, [a for ls in layers for a in ls],
+                               np.float64, setup)
+        # mh[0]: the flag word's low half (little-endian)
+        self._accept(call, int(mh[0]), torch.from_numpy(mh[1:].copy()) if C <= MAX_FUSED_CLIENTS else None)
+        return call.wrap(out)
 
     def _pair_streams(self, names, want: bool = True):
         """Every internal pair (u < v) of ``names``: its generator at the next
@@ -495,58 +512,37 @@ class SecureAggregator(Aggregator):
                 signs += [mu.sign(v) for v in later]
         return gens, signs
 
-    def _host_one_call(self, data, layer_lists, sizes, shapes, weights, average, is_list, payloads, digests_keep,
-                       C, n, sdev):
+    def _host_one_call(self, call: _Call):
         """The small call as ONE blocking library call
         (``sa_fused_clients_host_f32``: host arrays in, decoded result,
         digests and PRG flag out; the Python side only positions the pair
         streams).  None when the library has no fused kernel for C."""
-        names = [d.device.party for d in data]
-        pair_gens, pair_signs = self._pair_streams(names)
-        key = (C, n, str(sdev))
-        sc = getattr(self, "_one_call", None)
-        if sc is None or sc[0] != key:
-            pin_b, dev_b = K.host_fused_scratch(C, n)
-            sc = (key, torch.empty(pin_b, dtype=torch.uint8, pin_memory=True),
-                  torch.empty(dev_b, dtype=torch.uint8, device=sdev))
-            self._one_call = sc
+        pair_gens, pair_signs = self._pair_streams(call.names)
+        pin, dbuf = self._call_scratch(K.host_fused_scratch, call.C, call.n)
         xs = [ll[0] if len(ll) == 1 else np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in ll])
-              for ll in layer_lists]
-        ws = [1.0 if weights is None else float(w) for w in (weights or [None] * C)]
-        divisor = 1.0
-        if average:
-            divisor = float(C) if weights is None else float(sum(weights))
-        with torch.cuda.device(sdev):
-            got = K.fused_clients_host_f32(xs, ws, pair_gens, pair_signs, sc[1], sc[2], fxp_bits=self._fxp_bits,
-                                           divisor=divisor)
+              for ll in call.layer_lists]
+        with torch.cuda.device(self._device.torch_device):
+            got = K.fused_clients_host_f32(xs, call.scalar_weights(), pair_gens, pair_signs, pin, dbuf,
+                                           fxp_bits=self._fxp_bits, divisor=call.divisor())
         if got is None:
             return None
         out, digests, flag = got
-        if flag & L.SA_FLAG_PRG_REJECT:
-            raise _Rejected()
-        for nm in names:
-            self._maskers[nm].consume(n)
-        digests_keep.append(torch.from_numpy(digests.view(np.int64)))
-        self.last_digests = digests_keep
-        parts = np.split(out, np.cumsum(sizes)[:-1]) if len(sizes) > 1 else [out]
-        result = [p.reshape(sh) for p, sh in zip(parts, shapes)]
-        if not is_list:
-            return PYUObject(self._device, result[0])
-        return PYUObject(self._device, tuple(result) if isinstance(payloads[0], tuple) else result)
+        self._accept(call, flag, torch.from_numpy(digests.view(np.int64)))
+        return call.wrap(out)
 
-    def _host_general_shape(self, data, layer_lists, weights, n):
+    def _host_general_shape(self, call: _Call):
         """(element type, compute type, scalar weights) of host payloads of
         one element type in ``_NP2T`` with scalar weights of one compute type,
         every party on the server's GPU -- the shape the general host paths
         below take -- else None."""
-        C = len(data)
-        if (self._careful or self._keep_masked or not self._fused or C < 2 or n == 0
-                or any(d.device.gpu != self._device.gpu for d in data)):
+        C, weights = call.C, call.weights
+        if (self._careful or self._keep_masked or not self._fused or C < 2 or call.n == 0
+                or any(d.device.gpu != self._device.gpu for d in call.data)):
             return None
         if weights is not None and any(np.ndim(w) for w in weights):
             return None
         try:
-            dts = {np.asarray(a).dtype for ll in layer_lists for a in ll}
+            dts = {np.asarray(a).dtype for ll in call.layer_lists for a in ll}
         except Exception:  # noqa: BLE001 - ragged or exotic payloads: the general path decides
             return None
         if len(dts) != 1:
@@ -560,61 +556,36 @@ class SecureAggregator(Aggregator):
         ct = cts.pop()
         if ct not in _NP2T:
             return None
-        ws = [1.0 if weights is None else (float(w) if ct.kind == "f" else int(w)) for w in (weights or [None] * C)]
-        return xt, ct, ws
+        return xt, ct, call.scalar_weights(ct.kind)
 
-    def _host_general_one_call(self, data, layer_lists, sizes, shapes, weights, average, is_list, payloads,
-                               digests_keep):
+    def _host_general_one_call(self, call: _Call):
         """Host calls of float64 / int64 data (or float32 data with a float64
         compute type) of 2..9 parties on the server's GPU: small ones as ONE
         blocking library call (``sa_clients_host``: every party masked with
         its own streams into the sum, decode, one copy each way), large ones
         (any number of parties) chunked through ``_host_general_pipelined``.
         None when the call is of neither shape (the general path takes it)."""
-        C, n = len(data), sum(sizes)
-        got = self._host_general_shape(data, layer_lists, weights, n)
+        got = self._host_general_shape(call)
         if got is None:
             return None
         xt, ct, ws = got
-        if n * xt.itemsize > SMALL_CALL_BYTES:
+        if call.n * xt.itemsize > SMALL_CALL_BYTES:
             if not P.LARGE_PIPELINE:
                 return None
-            return self._host_general_pipelined(data, layer_lists, sizes, shapes, weights, average, is_list,
-                                                payloads, digests_keep, xt, ct, ws)
-        if C > 9:
+            return self._host_general_pipelined(call, xt, ct, ws)
+        if call.C > 9:
             return None
-        names = [d.device.party for d in data]
-        streams = [self._maskers[nm].streams(self._maskers[nm].peers) for nm in names]
+        streams = [self._maskers[nm].streams(self._maskers[nm].peers) for nm in call.names]
         xs = [np.asarray(ll[0]).reshape(-1) if len(ll) == 1 else
-              np.concatenate([np.asarray(a).reshape(-1) for a in ll]) for ll in layer_lists]
-        sdev = self._device.torch_device
-        key = (C, n, xt.itemsize, str(sdev))
-        sc = getattr(self, "_general_call", None)
-        if sc is None or sc[0] != key:
-            pin_b, dev_b = K.host_clients_scratch(C, n, xt.itemsize)
-            sc = (key, torch.empty(pin_b, dtype=torch.uint8, pin_memory=True),
-                  torch.empty(dev_b, dtype=torch.uint8, device=sdev))
-            self._general_call = sc
-        divisor = 1.0
-        if average:
-            divisor = float(C) if weights is None else float(sum(weights))
-        with torch.cuda.device(sdev):
-            out, digests, flag = K.clients_host(xs, ct, ws, streams, sc[1], sc[2], fxp_bits=self._fxp_bits,
-                                                divisor=divisor)
-        if flag & L.SA_FLAG_PRG_REJECT:
-            raise _Rejected()
-        for nm in names:
-            self._maskers[nm].consume(n)
-        digests_keep.append(torch.from_numpy(digests.view(np.int64)))
-        self.last_digests = digests_keep
-        parts = np.split(out, np.cumsum(sizes)[:-1]) if len(sizes) > 1 else [out]
-        result = [p.reshape(sh) for p, sh in zip(parts, shapes)]
-        if not is_list:
-            return PYUObject(self._device, result[0])
-        return PYUObject(self._device, tuple(result) if isinstance(payloads[0], tuple) else result)
+              np.concatenate([np.asarray(a).reshape(-1) for a in ll]) for ll in call.layer_lists]
+        pin, dbuf = self._call_scratch(K.host_clients_scratch, call.C, call.n, xt.itemsize)
+        with torch.cuda.device(self._device.torch_device):
+            out, digests, flag = K.clients_host(xs, ct, ws, streams, pin, dbuf, fxp_bits=self._fxp_bits,
+                                                divisor=call.divisor())
+        self._accept(call, flag, torch.from_numpy(digests.view(np.int64)))
+        return call.wrap(out)
 
-    def _host_general_pipelined(self, data, layer_lists, sizes, shapes, weights, average, is_list, payloads,
-                                digests_keep, xt, ct, ws):
+    def _host_general_pipelined(self, call: _Call, xt, ct, ws):
         """Large host payloads of the general shape (``_host_general_shape``:
         float64 / int64 data, or float32 data computed in float64), chunked
         through the three streams exactly like ``_host_fused_pipelined``:
@@ -625,88 +596,42 @@ class SecureAggregator(Aggregator):
         the device), the decode of chunk j, and its D2H into the result.
         Bit-identical to the one-shot general path: the same kernel, the same
         stream positions, element by element."""
-        from ... import hostpipe as H
-
         sdev = self._device.torch_device
-        C, n = len(data), sum(sizes)
-        ph = H.Phases("average" if average else "sum")
-        names = [d.device.party for d in data]
-        divisor = 1.0
-        if average:
-            divisor = float(C) if weights is None else float(sum(weights))
+        C, n, divisor = call.C, call.n, call.divisor()
         tx, tc = _NP2T[xt], _NP2T[ct]
-        layers = [H.host_layers(ll, xt) for ll in layer_lists]
+        layers = [H.host_layers(ll, xt) for ll in call.layer_lists]
         n_pad = -(-n // 4) * 4  # rows 16-byte aligned
         bounds = H.page_bounds(H.chunk_bounds(n), layers)
-        out = H.FreshOutput(n, np.float64, bounds)
-        s_in, s_k, s_out = H.streams(sdev)
-        with torch.cuda.device(sdev), H.Pinned([a for ls in layers for a in ls]) as pin:
-            ph.mark("register in")
-            cur = torch.cuda.current_stream(sdev)
+
+        def setup():
             x = torch.empty((C, n_pad), dtype=tx, device=sdev)
             ssum = torch.empty(n, dtype=K.U64, device=sdev)
             dec = torch.empty(n, dtype=torch.float64, device=sdev)
             masked = torch.empty(max(hi - lo for lo, hi in bounds), dtype=K.U64, device=sdev)
             meta = torch.zeros(1 + C, dtype=K.U64, device=sdev)  # flag word | digests
             flags = meta[:1].view(torch.int32)[:1]
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            s_in.wait_event(ready)
-            s_k.wait_event(ready)
+
+            def compute(j, lo, hi):
+                streams = [self._maskers[nm].streams(offset=lo) for nm in call.names]
+                ssum[lo:hi].zero_()
+                for c in range(C):
+                    K.mask(x[c, lo:hi], masked[:hi - lo], streams[c], weight=ws[c], compute_dtype=tc,
+                           fxp_bits=self._fxp_bits, sum_accum=ssum[lo:hi], digest=meta[1 + c:2 + c], flags=flags)
+                K.decode(ssum[lo:hi], dec[lo:hi], fxp_bits=self._fxp_bits, divisor=divisor)
 
             copies = [[(x[c, lo:hi], H.pieces(layers[c], lo, hi)) for c in range(C)] for lo, hi in bounds]
-            feed = H.Issued(s_in, copies, pin) if pin.ok else H.Feeder(s_in, copies)
-            try:
-                for j, (lo, hi) in enumerate(bounds):
-                    streams = [self._maskers[nm].streams(offset=lo) for nm in names]
-                    e_in, e_k = feed.ready(j), torch.cuda.Event()
-                    with torch.cuda.stream(s_k):
-                        s_k.wait_event(e_in)
-                        ssum[lo:hi].zero_()
-                        for c in range(C):
-                            K.mask(x[c, lo:hi], masked[:hi - lo], streams[c], weight=ws[c], compute_dtype=tc,
-                                   fxp_bits=self._fxp_bits, sum_accum=ssum[lo:hi], digest=meta[1 + c:2 + c],
-                                   flags=flags)
-                        K.decode(ssum[lo:hi], dec[lo:hi], fxp_bits=self._fxp_bits, divisor=divisor)
-                        e_k.record(s_k)
-                    out.copy_in(j, dec[lo:hi], s_out, e_k)
-                meta_h = torch.empty(1 + C, dtype=K.U64, pin_memory=True)
-                with torch.cuda.stream(s_k):
-                    meta_h.copy_(meta, non_blocking=True)
-                ph.mark("pipeline")
-            finally:
-                feed.join(check=False)
-                out.close()
-                s_k.synchronize()
-                s_out.synchronize()
-                s_in.synchronize()
-                cur.wait_stream(s_k)  # x, ssum, dec, masked, meta were allocated on the current stream
-            feed.join()
-            ph.mark("wait")
-        ph.mark("unregister")
-        ph.note(pinned=pin.ok, **pin.stats, **out.stats)
-        ph.done()
-        mh = meta_h.numpy()
-        if int(mh[0]) & L.SA_FLAG_PRG_REJECT:  # the flag word's low half (little-endian)
-            raise _Rejected()
-        for nm in names:
-            self._maskers[nm].consume(n)
-        digests_keep.append(torch.from_numpy(mh[1:].copy()))
-        self.last_digests = digests_keep
-        res = out.array
-        parts = np.split(res, np.cumsum(sizes)[:-1]) if len(sizes) > 1 else [res]
-        result = [p.reshape(sh) for p, sh in zip(parts, shapes)]
-        if not is_list:
-            return PYUObject(self._device, result[0])
-        return PYUObject(self._device, tuple(result) if isinstance(payloads[0], tuple) else result)
+            return copies, compute, lambda j: dec[bounds[j][0]:bounds[j][1]], meta
 
-    def _finish(self, data, groups, shapes, weights, average, as_torch, is_list, payloads, flags, masked_keep,
-                digests_keep):
+        out, mh = H.run_chunks("average" if call.average else "sum", sdev, bounds, [a for ls in layers for a in ls],
+                               np.float64, setup)
+        self._accept(call, int(mh[0]), torch.from_numpy(mh[1:].copy()))  # mh[0]: flag word in its low half
+        return call.wrap(out)
+
+    def _finish(self, call: _Call, groups, as_torch, flags, masked_keep, digests_keep):
         """Masked sum + decode of every launch group, split back into layers."""
         sdev = self._device.torch_device
-        server = self._device
-        nl = len(shapes)
-        out_layers = [None] * nl
+        data, shapes, weights = call.data, call.shapes, call.weights
+        out_layers = [None] * len(shapes)
         host_groups = []
         for lis, sizes, g in groups:
             n = g["n"]
@@ -722,16 +647,13 @@ class SecureAggregator(Aggregator):
             # decode on the server GPU: / 2^fxp, then / C or / sum(w)
             dec = torch.empty(n, dtype=torch.float64, device=sdev)
             divisor, divisor_vec = 1.0, None
-            if average:
-                if weights is None:
-                    divisor = float(len(data))
-                elif all(np.ndim(w) == 0 for w in weights):
-                    divisor = float(sum(weights))
-                else:
-                    li = lis[0]
-                    wb = [H.h2d(np.broadcast_to(np.asarray(w), shapes[li]).astype(np.float64).reshape(-1), sdev)
-                          for w in weights]
-                    divisor_vec = K.sum_f64(wb, torch.empty(n, dtype=torch.float64, device=sdev))
+            if call.average and weights is not None and any(np.ndim(w) for w in weights):
+                li = lis[0]
+                wb = [H.h2d(np.broadcast_to(np.asarray(w), shapes[li]).astype(np.float64).reshape(-1), sdev)
+                      for w in weights]
+                divisor_vec = K.sum_f64(wb, torch.empty(n, dtype=torch.float64, device=sdev))
+            else:
+                divisor = call.divisor()
             K.decode(s, dec, fxp_bits=self._fxp_bits, divisor=divisor, divisor_vec=divisor_vec)
             if as_torch:
                 for li, part in zip(lis, dec.split(sizes)):
@@ -761,10 +683,7 @@ class SecureAggregator(Aggregator):
         if self._keep_masked:
             self.last_masked = masked_keep
         self.last_digests = digests_keep
-        result = out_layers if is_list else out_layers[0]
-        if is_list and isinstance(payloads[0], tuple):
-            result = tuple(result)
-        return PYUObject(server, result)
+        return call.pack(out_layers)
 
     def _prepare_layer(self, data, arrays, shape, weights) -> dict:
         """Per-party device vector, arithmetic type and weight of one layer."""
