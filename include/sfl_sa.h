@@ -399,6 +399,41 @@ int sa_comm_gather_f64(void* comm, const double* send, double* recv, uint64_t co
 int sa_comm_info(void* comm, int* nranks, int* rank, int* device);
 int sa_comm_destroy(void* comm);
 
+/* ------------------------------------------------------------------ */
+/* Sparse ternary compression (fed_stc): the reference's STCSparse      */
+/* (sfl/utils/compressor/sparse_compressor.py:142-179) with the error   */
+/* feedback around it, on a worker (new - old + residual, sfl/ml/nn/fl/ */
+/* backend/torch/strategy/fed_stc.py:97-125) and on the server          */
+/* (aggregate + residual, server weights += sparse, sfl/ml/nn/fl/       */
+/* compress.py:28-42; fl_model.py:542-563).  For n elements of x_type   */
+/* T (SA_F32 or SA_F64), every operation rounded in T:                  */
+/*   u      = (a - b) + r          b, r optional: absent = not performed */
+/*   masked = the mask_num elements of smallest |u|, ordered by the bit */
+/*            pattern of |u| as an unsigned integer (numpy's order, NaN */
+/*            last); equal keys: the lower index is masked first        */
+/*            (np.argsort(kind="stable"); the reference's default sort  */
+/*            breaks such ties arbitrarily)                             */
+/*   mu     = T(S / (n - mask_num)), S the float64 sum of the survivors' */
+/*            |u| in an order that depends on n only (no float atomics: */
+/*            the same input gives the same bits); 0 when mask_num == n */
+/*   sparse_out = mu * sign(u_masked)   (a real multiply: NaN and inf   */
+/*            propagate as in numpy)                                    */
+/*   res_out    = u - sparse_out        (may alias r; nothing else may  */
+/*            alias)                                                    */
+/*   acc_inout += sparse_out            (optional: the server's weights) */
+/* A radix select on the key finds the threshold (no sort); threshold,  */
+/* tie quota and mu stay in device memory.  mu_out (optional) is one T  */
+/* on the device.  n >= 2^32 and other element types are refused.       */
+/* 16-byte aligned vectors take 16-byte loads and stores.               */
+/* ------------------------------------------------------------------ */
+
+/* bytes of device scratch sa_stc needs for n elements (8-byte aligned, its
+ * content is rewritten by every call), or a negative SA_ERR_* code */
+int sa_stc_scratch_bytes(uint64_t n, int x_type);
+
+int sa_stc(const void* a, const void* b, const void* r, int x_type, uint64_t n, uint64_t mask_num,
+           void* sparse_out, void* res_out, void* acc_inout, void* mu_out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

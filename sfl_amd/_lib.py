@@ -33,7 +33,7 @@ EXPORTED = (
     "sa_pcg64_raw_host", "sa_mask", "sa_fused_clients", "sa_fused_clients_host_f32", "sa_clients_host", "sa_mask_host", "sa_sum_decode_host", "sa_fused_bipartite", "sa_set_masking_reserve", "sa_sum_u64", "sa_decode",
     "sa_sum_f64", "sa_comm_unique_id", "sa_comm_init", "sa_comm_reduce_u64",
     "sa_comm_allreduce_u64", "sa_comm_reduce_scatter_u64", "sa_comm_alltoall_u64", "sa_comm_gather_f64", "sa_comm_info", "sa_comm_destroy", "sa_sumsq_f32", "sa_dp_perturb_f32", "sa_mask_dp",
-    "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64",
+    "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64", "sa_stc_scratch_bytes", "sa_stc",
 )
 
 
@@ -121,6 +121,8 @@ def _declare(lib):
     lib.sa_pcg64_find_zero.argtypes = [P(PCG64), i32, u64, vp, vp]
     lib.sa_stream_shift.argtypes = [vp, u64, P(PCG64), i32, u64, u64, vp]
     lib.sa_xor_u64.argtypes = [vp, u64, vp, vp]
+    lib.sa_stc_scratch_bytes.argtypes = [u64, i32]
+    lib.sa_stc.argtypes = [vp, vp, vp, i32, u64, u64, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED:
         if name not in ("sa_last_error",):
             getattr(lib, name).restype = i32

@@ -438,6 +438,44 @@ def mask_dp(x: torch.Tensor, out: torch.Tensor, streams: Sequence[tuple], dp: L.
 
 
 # ---------------------------------------------------------------------------
+# sparse ternary compression (sa_stc; fed_stc's worker and server halves)
+# ---------------------------------------------------------------------------
+def stc_scratch_bytes(n: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``stc`` needs for ``n`` elements of ``dtype``."""
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"stc: float32 or float64, not {dtype}")
+    rc = L.lib().sa_stc_scratch_bytes(int(n), xtype_of(dtype))
+    if rc < 0:
+        L.check(rc, "sa_stc_scratch_bytes")
+    return rc
+
+
+def stc(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, mask_num: int, sparse_out: torch.Tensor,
+        res_out: torch.Tensor, *, acc: torch.Tensor | None = None, mu_out: torch.Tensor | None = None,
+        scratch: torch.Tensor) -> torch.Tensor:
+    """u = (a - b) + r; mask the ``mask_num`` elements of smallest |u| (ties:
+    lower index first); sparse_out = mu * sign(u_masked) with mu the mean of
+    the survivors' |u|; res_out = u - sparse_out (may be ``r`` itself);
+    acc += sparse_out.  ``b``, ``r``, ``acc``, ``mu_out`` (one element) are
+    optional.  See sa_stc in include/sfl_sa.h."""
+    _require_gpu(a, b, r, sparse_out, res_out, acc, mu_out, scratch)
+    n = a.numel()
+    for t in (a, b, r, sparse_out, res_out, acc):
+        if t is not None and (t.dtype != a.dtype or t.numel() != n or not t.is_contiguous()):
+            raise ValueError("stc: contiguous tensors of one dtype and size")
+    if mu_out is not None and (mu_out.dtype != a.dtype or mu_out.numel() < 1):
+        raise ValueError("stc: mu_out is one element of the data's dtype")
+    if scratch.numel() * scratch.element_size() < stc_scratch_bytes(n, a.dtype):
+        raise ValueError("stc: scratch smaller than stc_scratch_bytes(n, dtype)")
+    if not 0 <= int(mask_num) <= n:
+        raise ValueError("stc: mask_num outside [0, n]")
+    L.check(L.lib().sa_stc(_ptr(a), _ptr(b), _ptr(r), xtype_of(a.dtype), n, int(mask_num), _ptr(sparse_out),
+                           _ptr(res_out), _ptr(acc), _ptr(mu_out), _ptr(scratch), C.c_void_p(_stream(a))),
+            "sa_stc")
+    return sparse_out
+
+
+# ---------------------------------------------------------------------------
 # numpy's rejection re-draw (after SA_FLAG_PRG_REJECT; never on the hot path)
 # ---------------------------------------------------------------------------
 U64_MAX = (1 << 64) - 1

@@ -1,0 +1,154 @@
+"""Sparse ternary compression (STC), the counterpart of the reference's
+``sfl/utils/compressor``: ``STCSparse`` (``sparse_compressor.py:142-179``)
+and the fused step the ``fed_stc`` worker and server run around it
+(``fed_stc.py:97-125``, ``compress.py:28-42``).
+
+The definition, for one tensor flattened to ``n`` elements of type T and
+``mask_num = round(sparse_rate * n)`` (Python's ``round``):
+
+1. ``u = (a - b) + r``, every operation rounded in T; an absent ``b`` or ``r``
+   means the operation is not performed.
+2. The ``mask_num`` elements of smallest ``|u|`` are masked, ordered by the
+   bit pattern of ``|u|`` as an unsigned integer (numpy's order, NaN last).
+   **Ties at the threshold: the lower index is masked first**
+   (``np.argsort(kind="stable")``).  The reference's default ``argsort`` is
+   unstable and breaks such ties arbitrarily; this rule is the one refinement.
+3. ``mu = T(S / (n - mask_num))``, ``S`` the float64 sum of the survivors'
+   ``|u|``; 0 when everything is masked.
+4. ``sparse = mu * sign(u_masked)``; ``res = u - sparse``; ``acc += sparse``.
+
+CUDA float32 / float64 tensors run the HIP kernels (``kernels.stc``, one
+radix select per tensor, nothing leaves the device) and give device tensors.
+numpy arrays and CPU tensors run a numpy implementation of the same
+definition, which CPU parties use; so do integer entries of a state dict
+(``num_batches_tracked``), computed in float64 as numpy would promote them.
+Host and device add ``S`` in different orders, so their ``mu`` may differ in
+the last bit; support and signs do not depend on that order.
+"""
+
+from __future__ import annotations
+
+from typing import List
+
+import numpy as np
+import torch
+
+_KEY = {np.dtype(np.float32): (np.uint32, np.uint32(0x7FFFFFFF)),
+        np.dtype(np.float64): (np.uint64, np.uint64(0x7FFFFFFFFFFFFFFF))}
+
+_scratch: dict = {}
+
+
+def mask_count(sparse_rate: float, n: int) -> int:
+    """The reference's ``round(self.sparse_rate * weight_len)``."""
+    return round(sparse_rate * n)
+
+
+def _check_rate(sparse_rate: float) -> None:
+    assert 0 <= sparse_rate <= 1, f"sparse rate should between 0 and 1, but get {sparse_rate}"
+
+
+def _stc_numpy(u: np.ndarray, mask_num: int):
+    """(sparse, mu) of flat float32 / float64 ``u``."""
+    n, T = u.size, u.dtype.type
+    kt, km = _KEY[u.dtype]
+    key = u.view(kt) & km
+    keep = np.ones(n, dtype=bool)
+    keep[np.argsort(key, kind="stable")[:mask_num]] = False
+    um = np.where(keep, u, T(0))
+    mu = T(0) if mask_num == n else T(np.sum(np.abs(um), dtype=np.float64) / (n - mask_num))
+    with np.errstate(invalid="ignore"):
+        return mu * np.sign(um), mu
+
+
+def _scratch_for(t: torch.Tensor) -> torch.Tensor:
+    """The device's scratch for the current stream, grown on demand."""
+    from .. import kernels as K
+
+    need = K.stc_scratch_bytes(t.numel(), t.dtype)
+    key = (t.device.index, K._stream(t))
+    s = _scratch.get(key)
+    if s is None or s.numel() < need:
+        s = _scratch[key] = torch.empty(need, dtype=torch.uint8, device=t.device)
+    return s
+
+
+def _step_device(a, b, r, sparse_rate, acc):
+    from .. import kernels as K
+
+    shape = a.shape
+    flat = [None if t is None else t.detach().contiguous().reshape(-1) for t in (a, b, r)]
+    n = flat[0].numel()
+    sparse = torch.empty(n, dtype=a.dtype, device=a.device)
+    res = torch.empty(n, dtype=a.dtype, device=a.device)
+    mu = torch.zeros((), dtype=a.dtype, device=a.device)
+    if acc is not None and (acc.dtype != a.dtype or acc.shape != shape or not acc.is_contiguous()
+                            or acc.device != a.device):
+        raise ValueError("stc_step: acc is a contiguous tensor of the data's dtype, shape and device")
+    if n:
+        K.stc(flat[0], flat[1], flat[2], mask_count(sparse_rate, n), sparse, res,
+              acc=None if acc is None else acc.detach().view(-1), mu_out=mu.view(1), scratch=_scratch_for(flat[0]))
+    return sparse.view(shape), res.view(shape), mu
+
+
+def _step_host(a, b, r, sparse_rate, acc):
+    u = np.asarray(a)
+    if b is not None:
+        u = np.subtract(u, np.asarray(b))
+    if r is not None:
+        u = np.add(u, np.asarray(r))
+    if u.dtype not in _KEY:  # integer state entries: float64, as numpy's mean * sign promotes them
+        u = u.astype(np.float64)
+    shape = u.shape
+    flat = np.ascontiguousarray(u).reshape(-1)
+    sparse, mu = _stc_numpy(flat, mask_count(sparse_rate, flat.size))
+    with np.errstate(invalid="ignore"):
+        res = np.subtract(flat, sparse)
+    sparse = sparse.reshape(shape)
+    if acc is not None:
+        if acc.dtype != sparse.dtype or acc.shape != shape:
+            raise ValueError("stc_step: acc has the data's dtype and shape")
+        np.add(acc, sparse, out=acc)
+    return sparse, res.reshape(shape), mu
+
+
+def stc_step(a, b, r, sparse_rate: float, acc=None):
+    """``(sparse, res, mu)`` of ``u = (a - b) + r`` (``b``, ``r`` optional) at
+    ``sparse_rate``; ``acc`` (optional) is updated in place with ``+= sparse``.
+    A worker calls it with (new weights, old weights, residual), the server
+    with (aggregated update, None, residual, acc=server weights).  CUDA
+    float32 / float64 tensors give device tensors (``mu`` a 0-d device
+    tensor: nothing is synchronised); numpy arrays give numpy arrays and CPU
+    tensors CPU tensors, through the numpy implementation."""
+    _check_rate(sparse_rate)
+    ts = [t for t in (a, b, r, acc) if t is not None]
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda and a.dtype in (torch.float32, torch.float64):
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+                raise ValueError("stc_step: every operand of a device step is a device tensor")
+            return _step_device(a, b, r, sparse_rate, acc)
+        if a.is_cuda:  # integer state entries: the numpy path, across pinned memory
+            from .. import hostpipe as H
+
+            host = [None if t is None else H.d2h(t, pooled=False) for t in (a, b, r, acc)]
+            sparse, res, mu = _step_host(*host[:3], sparse_rate, host[3])
+            if acc is not None:
+                acc.copy_(H.h2d(host[3], a.device))
+            return H.h2d(sparse, a.device), H.h2d(res, a.device), mu
+        host = [None if t is None else t.detach().numpy() for t in (a, b, r, acc)]  # views: acc in place
+        sparse, res, mu = _step_host(*host[:3], sparse_rate, host[3])
+        return torch.from_numpy(sparse), torch.from_numpy(res), mu
+    return _step_host(a, b, r, sparse_rate, acc)
+
+
+class STCSparse:
+    """The reference's ``STCSparse``: callable on a list of arrays, gives the
+    list of their ternary tensors (dense, the arrays' shapes)."""
+
+    def __init__(self, sparse_rate: float):
+        _check_rate(sparse_rate)
+        self.sparse_rate = sparse_rate
+        self.name = "STC"
+
+    def __call__(self, weights: List) -> List:
+        return [stc_step(w, None, None, self.sparse_rate)[0] for w in weights]
