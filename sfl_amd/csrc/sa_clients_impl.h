@@ -1003,9 +1003,6 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
 // ----------------------------------------------------------------------------
 // launcher
 // ----------------------------------------------------------------------------
-int occupancy_blocks(const void* kernel);  // sa_api.hip
-int masking_grid_cap(const void* kernel);  // sa_api.hip: occupancy less sa_set_masking_reserve's CUs
-
 // Buffer offsets are 32-bit byte offsets, so one launch covers at most
 // kChunkElems elements (4 GiB of u64); longer vectors are cut into chunks
 // whose streams start kChunkElems draws further on.

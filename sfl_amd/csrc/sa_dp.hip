@@ -13,8 +13,6 @@
 
 namespace sa {
 
-int occupancy_blocks(const void* kernel);  // sa_api.hip
-
 // per-block partial sums of x^2 in fp64 -> partials[blockIdx.x].  Two
 // non-temporal 16-byte loads in flight per lane at a 1,024-block grid: the
 // fastest of the forms tools/microbench/sumsq_rate.hip timed on MI355X

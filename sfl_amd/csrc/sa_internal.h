@@ -6,7 +6,7 @@ void sa_set_error(const char* fmt, ...);
 
 struct sa_mask_stream;
 struct sa_dp;
-// sa_mask with an optional fused GaussianModelDP pre-step (sa_api.hip)
+// sa_mask with an optional fused GaussianModelDP pre-step (sa_api.hip: the masking entries)
 int sa_mask_impl(const void* x, int x_type, int compute_type, uint64_t n, double weight, const void* weight_vec,
                  int fxp_bits, const struct sa_mask_stream* streams, int n_streams, uint64_t* out,
                  uint64_t* sum_accum, uint64_t* digest, uint32_t* flags, void* stream, const struct sa_dp* dp);
@@ -36,6 +36,13 @@ int sa_mask_impl(const void* x, int x_type, int compute_type, uint64_t n, double
 
 namespace sa {
 
+// sa_api.hip
+int occupancy_blocks(const void* kernel);  // active 256-thread blocks of `kernel` on the device; <= 0: error set
+int masking_grid_cap(const void* kernel);  // occupancy less sa_set_masking_reserve's CUs
+int check_type(int t, const char* what);   // SA_OK, or SA_ERR_ARG with "<what>: unknown element type" set
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+constexpr int kSumMaxIn = 32;    // inputs per launch of the server sums (sa_server.hip)
 constexpr int kMaxLocal = 8;     // co-located clients per fused launch
 constexpr int kMaxStreams = 32;  // mask streams per launch (kernel-arg resident)
 constexpr int kMaskPass = 16;    // streams per pass of the single-client kernel

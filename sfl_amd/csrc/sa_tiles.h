@@ -1,5 +1,5 @@
 // sa_tiles.h -- workgroup -> tile mapping of the one-pass streaming kernels
-// (device code: included by sa_api.hip and sa_dp.hip after hip_runtime.h)
+// (device code: included by sa_server.hip and sa_dp.hip after hip_runtime.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -69,6 +69,12 @@ def make_streams(entries: Sequence[tuple]) -> C.Array:
     return arr
 
 
+def _pair_arrays(n_clients: int, pair_gens: Sequence, pair_signs: Sequence[int]) -> tuple[C.Array, C.Array]:
+    """sa_pcg64[] / int8[] of the n_clients * (n_clients - 1) / 2 internal pairs (never empty arrays)"""
+    npair = n_clients * (n_clients - 1) // 2
+    return (L.PCG64 * max(1, npair))(*pair_gens), (C.c_int8 * max(1, npair))(*[int(s) for s in pair_signs])
+
+
 def mask(x: torch.Tensor | None, out: torch.Tensor, streams: Sequence[tuple], *,
          weight: float = 1.0, weight_vec: torch.Tensor | None = None, compute_dtype=None,
          fxp_bits: int = 18, x_dtype=None, sum_accum: torch.Tensor | None = None,
@@ -106,9 +112,7 @@ def fused_clients(xs: Sequence[torch.Tensor], weights: Sequence[float], pair_gen
         clients[c].weight = float(weights[c])
         mo = masked_outs[c] if masked_outs else None
         clients[c].masked_out = mo.data_ptr() if mo is not None else None
-    npair = nc * (nc - 1) // 2
-    pg = (L.PCG64 * max(1, npair))(*pair_gens)
-    ps = (C.c_int8 * max(1, npair))(*[int(s) for s in pair_signs])
+    pg, ps = _pair_arrays(nc, pair_gens, pair_signs)
     carr = make_streams(cross)
     rc = L.lib().sa_fused_clients(clients, nc, xtype_of(xs[0].dtype), n, int(fxp_bits), pg, ps,
                                   carr, int(n_cross), _ptr(sum_out), int(bool(accumulate)),
@@ -237,9 +241,21 @@ def decode(s: torch.Tensor, out: torch.Tensor, *, fxp_bits: int = 18, divisor: f
     return out
 
 
+def _scratch(pinned: torch.Tensor, dev: torch.Tensor, need_pin: int, need_dev: int) -> None:
+    _require_gpu(dev)
+    if not pinned.is_pinned() or pinned.numel() < need_pin or dev.numel() < need_dev:
+        raise ValueError("scratch buffers too small or not page-locked")
+
+
+def _pad_meta(n: int, meta_words: int) -> tuple[int, int]:
+    """(n_pad, meta words rounded to even) of csrc/sa_host_layout.h, which tests/test_boundary.py holds the
+    four ``*_scratch`` below equal to; not asked of the library: a small call counts microseconds (``_stream``)."""
+    return -(-n // 4) * 4, (meta_words + 1) // 2 * 2
+
+
 def host_fused_scratch(n_clients: int, n: int) -> tuple[int, int]:
     """(pinned bytes, device bytes) sa_fused_clients_host_f32 needs."""
-    n_pad, meta = -(-n // 4) * 4, (n_clients + 2) // 2 * 2  # flag + digests, an even word count
+    n_pad, meta = _pad_meta(n, 1 + n_clients)  # flag + digests
     pin = n_clients * n_pad * 4 + (meta + n_pad) * 8
     return pin, pin + n_pad * 8
 
@@ -252,19 +268,14 @@ def fused_clients_host_f32(xs: Sequence[np.ndarray], weights: Sequence[float], p
     sa_fused_clients_host_f32 in include/sfl_sa.h).  ``pinned`` / ``dev``:
     byte tensors of host_fused_scratch's sizes (page-locked / on the GPU).
     None when the library has no fused kernel for this client count."""
-    _require_gpu(dev)
     nc, n = len(xs), int(xs[0].size)
-    need_pin, need_dev = host_fused_scratch(nc, n)
-    if not pinned.is_pinned() or pinned.numel() < need_pin or dev.numel() < need_dev:
-        raise ValueError("scratch buffers too small or not page-locked")
+    _scratch(pinned, dev, *host_fused_scratch(nc, n))
     arrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in xs]
     if any(a.size != n for a in arrs):
         raise ValueError("fused clients need equal-size vectors")
     ptrs = (C.c_void_p * nc)(*[a.ctypes.data for a in arrs])
     ws = (C.c_double * nc)(*[float(w) for w in weights])
-    npair = nc * (nc - 1) // 2
-    pg = (L.PCG64 * max(1, npair))(*pair_gens)
-    ps = (C.c_int8 * max(1, npair))(*[int(s) for s in pair_signs])
+    pg, ps = _pair_arrays(nc, pair_gens, pair_signs)
     out = np.empty(n, dtype=np.float64)
     digests = np.empty(nc, dtype=np.uint64)
     flags = C.c_uint32(0)
@@ -283,7 +294,7 @@ _NP_XTYPE = {np.dtype(np.float32): L.SA_F32, np.dtype(np.float64): L.SA_F64, np.
 
 def host_clients_scratch(n_clients: int, n: int, itemsize: int) -> tuple[int, int]:
     """(pinned bytes, device bytes) sa_clients_host needs."""
-    n_pad, meta = -(-n // 4) * 4, (n_clients + 2) // 2 * 2
+    n_pad, meta = _pad_meta(n, 1 + n_clients)
     pin = n_clients * n_pad * itemsize + (2 * n_pad + meta) * 8
     return pin, pin + n_clients * n_pad * 8
 
@@ -295,15 +306,12 @@ def clients_host(xs: Sequence[np.ndarray], compute_dtype, weights: Sequence[floa
     (gen, sign, peer) triples) -> (decoded float64 host array, uint64
     digests, flag word) in ONE blocking call (sa_clients_host in
     include/sfl_sa.h)."""
-    _require_gpu(dev)
     nc, n = len(xs), int(np.asarray(xs[0]).size)
     dt = np.asarray(xs[0]).dtype
     arrs = [np.ascontiguousarray(x, dtype=dt).reshape(-1) for x in xs]
     if dt not in _NP_XTYPE or any(a.size != n for a in arrs):
         raise ValueError("host clients need equal-size float32 / float64 / int64 vectors of one type")
-    need_pin, need_dev = host_clients_scratch(nc, n, dt.itemsize)
-    if not pinned.is_pinned() or pinned.numel() < need_pin or dev.numel() < need_dev:
-        raise ValueError("scratch buffers too small or not page-locked")
+    _scratch(pinned, dev, *host_clients_scratch(nc, n, dt.itemsize))
     if any(len(st) != nc - 1 for st in streams):
         raise ValueError("every client needs n_clients - 1 streams")
     ptrs = (C.c_void_p * nc)(*[a.ctypes.data for a in arrs])
@@ -320,16 +328,10 @@ def clients_host(xs: Sequence[np.ndarray], compute_dtype, weights: Sequence[floa
     return out, digests, int(flags.value)
 
 
-def _scratch(pinned: torch.Tensor, dev: torch.Tensor, need_pin: int, need_dev: int) -> None:
-    _require_gpu(dev)
-    if not pinned.is_pinned() or pinned.numel() < need_pin or dev.numel() < need_dev:
-        raise ValueError("scratch buffers too small or not page-locked")
-
-
 def mask_host_scratch(n: int, itemsize: int) -> tuple[int, int]:
     """(pinned bytes, device bytes) sa_mask_host needs."""
-    n_pad = -(-n // 4) * 4
-    return n_pad * itemsize + (2 + n_pad) * 8, n_pad * itemsize + (2 + n_pad) * 8
+    n_pad, meta = _pad_meta(n, 2)  # the flag word + pad
+    return n_pad * itemsize + (meta + n_pad) * 8, n_pad * itemsize + (meta + n_pad) * 8
 
 
 def mask_host(x: np.ndarray, compute_dtype, streams: Sequence[tuple], pinned: torch.Tensor, dev: torch.Tensor, *,
@@ -353,7 +355,7 @@ def mask_host(x: np.ndarray, compute_dtype, streams: Sequence[tuple], pinned: to
 
 def sum_decode_host_scratch(n_clients: int, n: int) -> tuple[int, int]:
     """(pinned bytes, device bytes) sa_sum_decode_host needs."""
-    n_pad, meta = -(-n // 4) * 4, (n_clients + 1) // 2 * 2
+    n_pad, meta = _pad_meta(n, n_clients)
     pin = (n_clients * n_pad + meta + n_pad) * 8
     return pin, pin + n_pad * 8
 

@@ -271,3 +271,87 @@ def test_ctypes_structs_match_the_header_layout(tmp_path):
         assert got[(name, "size")] == C.sizeof(cls), name
         for f in fields:
             assert got[(name, f)] == getattr(cls, f).offset, (name, f)
+
+
+_LAYOUT_PROGRAM = r"""
+#include <stdio.h>
+#include "sa_host_layout.h"
+using namespace sa;
+
+static int bad = 0;
+#define REQUIRE(cond)                                                                            \
+  do {                                                                                           \
+    if (!(cond)) {                                                                               \
+      printf("FAIL %s C=%llu n=%llu es=%llu: %s\n", e, (unsigned long long)C, (unsigned long long)n, \
+             (unsigned long long)es, #cond);                                                     \
+      bad = 1;                                                                                   \
+    }                                                                                            \
+  } while (0)
+
+// the regions in order, none overlapping, and every offset a 16-byte kernel is handed a multiple of 16:
+// inputs | sum (sum_bytes) | meta (meta_words used) | result (n_pad 8-byte elements) | tail (tail_vecs vectors)
+static void check(const char* e, const HostLayout& l, uint64_t C, uint64_t n, uint64_t es, uint64_t sum_bytes,
+                  uint64_t meta_words, uint64_t tail_vecs) {
+  const uint64_t np = n_pad(n);
+  REQUIRE(np >= n && np % 4 == 0 && np - n < 4);
+  REQUIRE(l.in_stride >= n * es && l.in_stride % 16 == 0);  // every staged input starts 16-byte aligned
+  REQUIRE(C * l.in_stride <= l.zeroed);
+  REQUIRE(l.zeroed % 16 == 0 && l.zeroed + sum_bytes == l.meta);  // the sum
+  REQUIRE(l.meta % 8 == 0 && l.meta + meta_words * 8 <= l.result);
+  REQUIRE(l.result % 16 == 0 && l.result + np * 8 <= l.pinned_bytes);
+  REQUIRE(l.tail % 16 == 0 && l.tail >= l.pinned_bytes && (np * 8) % 16 == 0);  // tail vectors np * 8 apart
+  REQUIRE(l.tail + tail_vecs * np * 8 <= l.dev_bytes);
+  REQUIRE(l.zero_by_copy == (sum_bytes <= (16u << 10)));
+  printf("%s %llu %llu %llu %llu %llu\n", e, (unsigned long long)C, (unsigned long long)n, (unsigned long long)es,
+         (unsigned long long)l.pinned_bytes, (unsigned long long)l.dev_bytes);
+}
+
+int main() {
+  const uint64_t ns[] = {1, 2, 3, 4, 5, 2047, 2048, 2049, 1000003};
+  for (uint64_t n : ns) {
+    for (uint64_t C = 2; C <= 8; C++) check("fused", fused_host_layout(C, n), C, n, 4, 0, 1 + C, 1);
+    for (uint64_t es = 4; es <= 8; es += 4) {
+      for (uint64_t C = 2; C <= 9; C++)
+        check("clients", clients_host_layout(C, n, es), C, n, es, n_pad(n) * 8, 1 + C, C);
+      check("mask", mask_host_layout(n, es), 1, n, es, 0, 1, 0);
+    }
+    for (uint64_t C = 1; C <= 32; C++) check("sum_decode", sum_decode_host_layout(C, n), C, n, 8, 0, C, 1);
+  }
+  return bad;
+}
+"""
+
+
+def test_scratch_sizes_match_the_c_layout(tmp_path):
+    """kernels.*_scratch (what callers allocate) equal pinned_bytes /
+    dev_bytes of csrc/sa_host_layout.h (what the four blocking entries write),
+    compiled alone with g++, over n at the n_pad roundings and both sides of
+    sa_clients_host's 16 KiB zero-by-copy threshold, every legal client count
+    and both element sizes; the program itself checks that the regions do not
+    overlap and that every offset handed to a 16-byte kernel is 16-byte
+    aligned.  A Python formula one word short would be an out-of-bounds
+    device write."""
+    import shutil
+    import subprocess
+
+    from sfl_amd import kernels as K
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    src = tmp_path / "layout.cpp"
+    src.write_text(_LAYOUT_PROGRAM)
+    exe = tmp_path / "layout"
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "sfl_amd", "csrc"), str(src), "-o",
+                        str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+    python = {"fused": lambda C, n, es: K.host_fused_scratch(C, n),
+              "clients": K.host_clients_scratch,
+              "mask": lambda C, n, es: K.mask_host_scratch(n, es),
+              "sum_decode": lambda C, n, es: K.sum_decode_host_scratch(C, n)}
+    lines = r.stdout.splitlines()
+    assert len(lines) == 9 * (7 + 2 * (8 + 1) + 32)
+    for ln in lines:
+        e, C, n, es, pin, dev = ln.split()
+        assert python[e](int(C), int(n), int(es)) == (int(pin), int(dev)), ln

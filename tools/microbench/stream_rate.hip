@@ -1,5 +1,5 @@
 // HBM streaming shapes on MI355X, to choose the server kernels' form
-// (sfl_amd/csrc/sa_api.hip: k_sum_u64, k_decode, k_sum_f64).  Every case
+// (sfl_amd/csrc/sa_server.hip: k_sum, k_decode).  Every case
 // moves 16-B per lane per access; what varies: accesses in flight per lane
 // (U), grid (occupancy-sized grid-stride loop vs one tile per block), and
 // non-temporal loads/stores.  Cases: copy (1 read : 1 write, decode's

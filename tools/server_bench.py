@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""HBM roofline of the server kernels (sfl_amd/csrc/sa_api.hip), not the
-headline bench: k_sum_u64 (the wire path's server sum, k masked vectors),
-k_decode (scalar divisor: the sum / unweighted average; per-element divisor
-vector: per-element weights) and k_sum_f64 (the divisor vector's sum of
-weight arrays), each at --elems element positions, timed with HIP events
+"""HBM roofline of the server kernels (sfl_amd/csrc/sa_server.hip), not the
+headline bench: k_sum_u64 (k_sum over uint64: the wire path's server sum, k
+masked vectors), k_decode (scalar divisor: the sum / unweighted average;
+per-element divisor vector: per-element weights) and k_sum_f64 (k_sum over
+float64: the divisor vector's sum of weight arrays), each at --elems element positions, timed with HIP events
 (median of --reps launches after warm-up), one JSON line per kernel with its
 algorithmic bytes and the fraction of the 8 TB/s HBM peak.
 
