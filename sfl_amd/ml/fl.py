@@ -36,9 +36,13 @@ ternary compression up- and downstream, ``fed_stc.py:42-143`` on the
 workers, ``fl_model.py:542-556`` / ``compress.py:28-42`` on the server)
 because it is the reference's bandwidth-reducing strategy: its per-element
 work runs in the HIP kernels of ``sfl_amd.utils.compressor`` wherever
-``compress_device`` is a GPU.  The ternary tensors travel dense: the secure
-aggregator has no sparse input (the reference's ``sparse_encode`` feeds its
-plain, debugging aggregator only).  ``fed_scr`` (structure-wise pruning of
+``compress_device`` is a GPU.  By default the ternary tensors travel dense:
+the secure aggregator masks every element and has no sparse input.
+``sparse_transport`` ("down" or "both") puts them into COO form
+(``sfl_amd.utils.sparse``, built on the host) as the reference's ``sparse_encode`` does at the
+end of ``train_step`` (``fed_stc.py:128``, ``fed_scr.py:126``) and on the
+server's downstream (``fl_model.py:558-563``); sparse uploads ("both") need
+an aggregator that takes them, ``SparsePlainAggregator``.  ``fed_scr`` (structure-wise pruning of
 the upload, ``fed_scr.py:42-139``; the server passes it through,
 ``compress.py:56-57``) is the reference's other compression strategy and
 shares ``fed_stc``'s worker flow; its kernels are ``sa_scr``'s.
@@ -359,10 +363,11 @@ class FedSTC(FedAvgW):
 
     def __init__(self, builder: TorchModel, device: PYU, random_seed: Optional[int] = None,
                  train_device: Optional[torch.device] = None, sparsity: float = 0.0, compress_device=None,
-                 **kwargs):
+                 sparse_transport: Optional[str] = None, **kwargs):
         super().__init__(builder, device, random_seed, train_device)
         assert 0 <= sparsity <= 1, f"sparse rate should between 0 and 1, but get {sparsity}"
         self.sparsity = float(sparsity)
+        self.sparse_transport = sparse_transport  # None / "down" / "both" (FLModel checks the value)
         self.compress_device = torch.device(compress_device) if compress_device is not None else self.exe_device
         # device-resident: a GPU model compressed on its own GPU
         self._resident = self.exe_device.type != "cpu" and self.compress_device == self.exe_device
@@ -385,6 +390,24 @@ class FedSTC(FedAvgW):
                                   else np.asarray(u)))
         return out
 
+    def _upload(self, payload: list) -> list:
+        """What leaves the worker: with ``sparse_transport="both"`` the COO
+        form of the payload (fed_stc.py:128)."""
+        if self.sparse_transport != "both":
+            return payload
+        from ..utils.compressor import sparse_encode
+
+        return sparse_encode(payload)
+
+    @staticmethod
+    def _dense(updates):
+        """The downstream update, decoded if it came in COO form (fed_stc.py:71, :141)."""
+        from ..utils.sparse import SparseCOO, sparse_decode
+
+        if updates is not None and any(isinstance(u, SparseCOO) for u in updates):
+            return sparse_decode(updates)
+        return updates
+
     def _compress(self, a, b, r):
         """One layer's (payload, residual).  Float layers run on
         ``compress_device``; integer entries take the numpy path."""
@@ -402,6 +425,7 @@ class FedSTC(FedAvgW):
         self.model.train()
         if refresh_data:
             self._reset_data_iter()
+        updates = self._dense(updates)
         if updates is not None:  # fed_stc.py:69-73
             self.set_weights(self._plus(self.model_weights, updates))
         self.model_weights = self._state()  # :78
@@ -430,9 +454,10 @@ class FedSTC(FedAvgW):
             pairs = [self._compress(n, o, r) for n, o, r in zip(new, self.model_weights, res)]
         self._res = [p[1] for p in pairs]
         self.set_weights(self.model_weights)  # :126
-        return [p[0] for p in pairs], num_sample
+        return self._upload([p[0] for p in pairs]), num_sample
 
     def apply_weights(self, updates, **kwargs):
+        updates = self._dense(updates)
         if updates is not None:  # fed_stc.py:139-143
             self.set_weights(self._plus(self.model_weights, updates))
 
@@ -454,8 +479,9 @@ class FedSCR(FedSTC):
 
     def __init__(self, builder: TorchModel, device: PYU, random_seed: Optional[int] = None,
                  train_device: Optional[torch.device] = None, threshold: float = 0.0, compress_device=None,
-                 keep_residual: bool = False, **kwargs):
-        super().__init__(builder, device, random_seed, train_device, sparsity=0.0, compress_device=compress_device)
+                 keep_residual: bool = False, sparse_transport: Optional[str] = None, **kwargs):
+        super().__init__(builder, device, random_seed, train_device, sparsity=0.0, compress_device=compress_device,
+                         sparse_transport=sparse_transport)
         self.threshold = float(threshold)
         self.keep_residual = bool(keep_residual)
 
@@ -483,15 +509,38 @@ _STRATEGIES = {("fed_stc", "torch"): FedSTC, ("fed_scr", "torch"): FedSCR, ("fed
 
 class FLModel:
     """Horizontal FL over ``device_list`` with ``aggregator`` (any object with
-    the ``Aggregator`` surface: ``average(data, axis, weights)``)."""
+    the ``Aggregator`` surface: ``average(data, axis, weights)``).
+
+    ``sparse_transport`` (``fed_stc`` / ``fed_scr`` only; default None: dense,
+    as before): ``"down"`` sends the server's compressed update to the
+    parties in COO form (``fed_stc``; ``fed_scr``'s downstream is not
+    compressed and stays dense) and works with any aggregator; ``"both"``
+    also uploads in COO form and needs an aggregator that declares
+    ``accepts_sparse`` (``SparsePlainAggregator``).  When it is set,
+    ``history`` has ``upload_bytes`` and ``download_bytes``, one entry per
+    round: the bytes of all parties' uploads and of all parties' copies of
+    the downstream payload."""
 
     def __init__(self, server: Optional[PYU] = None, device_list: List[PYU] = (), model: TorchModel = None,
                  aggregator=None, strategy: str = "fed_avg_w", backend: str = "torch",
-                 random_seed: Optional[int] = None, train_device=None, dp_strategy=None, **kwargs):
+                 random_seed: Optional[int] = None, train_device=None, dp_strategy=None,
+                 sparse_transport: Optional[str] = None, **kwargs):
         if (strategy, backend) not in _STRATEGIES:
             raise NotImplementedError(f"strategy {strategy!r} / backend {backend!r}")
         if aggregator is None:
             raise ValueError("this build aggregates through an Aggregator (server_agg_method is out of scope)")
+        if sparse_transport is not None:
+            if sparse_transport not in ("down", "both"):
+                raise ValueError(f"sparse_transport is None, 'down' or 'both', not {sparse_transport!r}")
+            if strategy not in ("fed_stc", "fed_scr"):
+                raise ValueError(f"sparse_transport needs a compressing strategy (fed_stc, fed_scr), not {strategy!r}")
+            if sparse_transport == "both" and not getattr(aggregator, "accepts_sparse", False):
+                raise ValueError(
+                    f"sparse_transport='both' needs an aggregator that takes sparse uploads (accepts_sparse, "
+                    f"SparsePlainAggregator); {type(aggregator).__name__} does not: a secure aggregator masks "
+                    f"every element, so its uploads stay dense.  sparse_transport='down' is what it can use")
+            kwargs["sparse_transport"] = sparse_transport
+        self.sparse_transport = sparse_transport
         self.server = server
         self.device_list = list(device_list)
         self._aggregator = aggregator
@@ -502,6 +551,11 @@ class FLModel:
         self._workers: Dict[PYU, FedAvgW] = {
             d: _STRATEGIES[(strategy, backend)](model, d, random_seed, train_device, **kwargs)
             for d in self.device_list}
+        if sparse_transport is not None and any(w._resident for w in self._workers.values()):
+            raise ValueError("sparse_transport: the COO form is built on the host (it has no device kernel yet), and "
+                             "a GPU model compressed on its own GPU keeps its payload on the device; train with "
+                             "train_device='cpu' (compress_device may be the GPU: the payload then comes back "
+                             "through pinned memory)")
 
     def initialize_weights(self):
         """Average the clients' initial weights through the aggregator and
@@ -524,6 +578,10 @@ class FLModel:
         steps = max(w.steps_per_epoch() for w in self._workers.values())
         history = {"train_loss": [], "val_loss": [], "val_accuracy": [], "aggregation_s": [], "round_s": [],
                    "init_s": 0.0, "eval_s": 0.0}
+        if self.sparse_transport is not None:
+            from ..utils.sparse import payload_nbytes, sparse_encode
+
+            history["upload_bytes"], history["download_bytes"] = [], []
         # reference fit (fl_model.py:473): the initial weights are averaged
         # through the aggregator before the first epoch
         t_init = time.perf_counter()
@@ -548,6 +606,8 @@ class FLModel:
                                         dp_strategy=self.dp_strategy)
                     params.append(PYUObject(d, p))
                     nums.append(n)
+                if self.sparse_transport is not None:
+                    history["upload_bytes"].append(sum(payload_nbytes(p.data) for p in params))
                 t_agg = time.perf_counter()
                 model_params = self._aggregator.average(params, axis=0, weights=nums)
                 agg_data = reveal(model_params)
@@ -564,13 +624,24 @@ class FLModel:
                             not isinstance(server_weight[0], torch.Tensor):
                         # device payloads: the server's copy follows the aggregate onto its device
                         server_weight = [H.h2d(w, a.device) for w, a in zip(server_weight, agg_data)]
+                    # a plain aggregator's unweighted initial average keeps the model's float32 while
+                    # its weighted averages are float64 (numpy's promotion): the server's copy follows
+                    # the aggregate's type too (a no-op with an aggregator whose results are all float64)
+                    server_weight = [w if w.dtype == a.dtype else
+                                     (w.to(a.dtype) if isinstance(w, torch.Tensor) else w.astype(a.dtype))
+                                     for w, a in zip(server_weight, agg_data)]
                     res = self._res or [None] * len(agg_data)
                     steps_out = [stc_step(a, None, r, self._sparsity, acc=w)
                                  for a, r, w in zip(agg_data, res, server_weight)]
                     self._res = [s[1] for s in steps_out]
                     agg_data = [s[0] for s in steps_out]
-                    model_params = PYUObject(model_params.device, agg_data)
+                    down = agg_data
+                    if self.sparse_transport is not None:  # fl_model.py:558-563
+                        down = sparse_encode(agg_data)
+                    model_params = PYUObject(model_params.device, down)
                     self.server_weight = server_weight
+                if self.sparse_transport is not None:
+                    history["download_bytes"].append(len(self.device_list) * payload_nbytes(reveal(model_params)))
                 model_params_list = [model_params.to(d) for d in self.device_list]
                 history["round_s"].append(time.perf_counter() - t_round)
                 if round_hook is not None:

@@ -29,6 +29,10 @@ Structure-wise pruning (SCR), the reference's ``SCRSparse``
 (``sparse_compressor.py:182-230``) and the ``fed_scr`` worker's step around it
 (``fed_scr.py:97-125``), is ``scr_step`` / ``SCRSparse`` at the end of this
 file; its definition stands in ``scr_step``'s docstring.
+
+The COO transport of what the two compressors produce (``sparse_encode`` /
+``sparse_decode``, ``sparse_compressor.py:234-284``) lives in
+``sfl_amd.utils.sparse`` and is re-exported here.
 """
 
 from __future__ import annotations
@@ -293,3 +297,6 @@ class SCRSparse:
 
     def __call__(self, weights: List) -> List:
         return [scr_step(w, None, None, self.threshold, want_res=False)[0] for w in weights]
+
+
+from .sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode  # noqa: E402,F401
