@@ -1,7 +1,7 @@
 // sa_elems.h — a lane's four consecutive elements of a tile, for streaming
-// kernels (sa_scr.hip; sa_stc.hip has the same helpers of its own): 16-byte
-// loads and stores where the caller found every vector 16-byte aligned,
-// element accesses with the same lane-to-element map otherwise.
+// kernels (sa_stc.hip, sa_scr.hip): 16-byte loads and stores where the
+// caller found every vector 16-byte aligned, element accesses with the same
+// lane-to-element map otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

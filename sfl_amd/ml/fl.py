@@ -60,6 +60,8 @@ import torch
 
 from .. import hostpipe as H
 from ..device import PYU, PYUObject, reveal
+from ..utils.compressor import scr_step, stc_step
+from ..utils.sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode
 
 
 def _host_array(v: torch.Tensor) -> np.ndarray:
@@ -161,27 +163,50 @@ class FedAvgW:
         model.load_state_dict(new)
 
     # ------------------------------------------------------- training
-    def train_step(self, weights, cur_steps: int, train_steps: int, refresh_data: bool = False,
-                   dp_strategy=None, **kwargs):
+    # What every strategy's train_step shares; a strategy overrides the hook
+    # that differs (_loss, _train_batch) and keeps its own payload around them.
+    def _begin_step(self, refresh_data: bool):
         self.model.train()
         if refresh_data:
             self._reset_data_iter()
-        if weights is not None:
-            self.set_weights(weights)
+
+    def _loss(self, x, y):
+        return self.loss_fn(self.model(x), y)
+
+    def _train_batch(self, x, y):
+        """One local step on one batch; gives its loss."""
+        self.optimizer.zero_grad()
+        loss = self._loss(x, y)
+        loss.backward()
+        self.optimizer.step()
+        return loss
+
+    def _train(self, train_steps: int) -> int:
+        """``train_steps`` batches in order through ``_train_batch``; sets
+        ``last_loss`` and gives the number of samples seen."""
         num_sample = 0
         loss = None
         for _ in range(train_steps):
             x, y = self.next_batch()
             num_sample += x.shape[0]
-            self.optimizer.zero_grad()
-            loss = self.loss_fn(self.model(x), y)
-            loss.backward()
-            self.optimizer.step()
+            loss = self._train_batch(x, y)
         self.last_loss = float(loss.item()) if loss is not None else float("nan")
-        model_weights = self.get_weights(return_numpy=True)
-        if dp_strategy is not None and dp_strategy.model_gdp is not None:  # fed_avg_w.py:80-85
-            model_weights = dp_strategy.model_gdp(model_weights)
-        return model_weights, num_sample
+        return num_sample
+
+    @staticmethod
+    def _model_gdp(payload, dp_strategy):
+        """The payload after the strategy's model-level DP, if it has one (fed_avg_w.py:80-85)."""
+        if dp_strategy is not None and dp_strategy.model_gdp is not None:
+            return dp_strategy.model_gdp(payload)
+        return payload
+
+    def train_step(self, weights, cur_steps: int, train_steps: int, refresh_data: bool = False,
+                   dp_strategy=None, **kwargs):
+        self._begin_step(refresh_data)
+        if weights is not None:
+            self.set_weights(weights)
+        num_sample = self._train(train_steps)
+        return self._model_gdp(self.get_weights(return_numpy=True), dp_strategy), num_sample
 
     def apply_weights(self, weights, **kwargs):
         if weights is not None:
@@ -221,40 +246,30 @@ class MOON(FedAvgW):
         self.prev_model_list: List[torch.nn.Module] = []
         self.global_model = copy.deepcopy(self.model)
 
+    def _loss(self, x, y):  # moon.py:76-97
+        _, pro1, y_pred = self.model(x, return_all=True)
+        loss = self.loss_fn(y_pred, y)
+        _, pro2, _ = self.global_model(x, return_all=True)
+        logits = self.model.cosine_similarity_fn(pro1, pro2).reshape(-1, 1)
+        for pre in self.prev_model_list:
+            _, pro3, _ = pre(x, return_all=True)
+            nega = self.model.cosine_similarity_fn(pro1, pro3)
+            logits = torch.cat((logits, nega.reshape(-1, 1)), dim=1)
+        logits = logits / self.model.temperature
+        labels = torch.zeros(x.size(0), dtype=torch.long, device=x.device)
+        return loss + self.model.mu * self.loss_fn(logits, labels)
+
     def train_step(self, weights, cur_steps: int, train_steps: int, refresh_data: bool = False,
                    dp_strategy=None, **kwargs):
-        self.model.train()
-        if refresh_data:
-            self._reset_data_iter()
+        self._begin_step(refresh_data)
         if weights is not None:  # moon.py:64-72: global model <- aggregated weights, frozen
             self.set_weights(weights, model=self.global_model)
             self.global_model.eval()
             for prm in self.global_model.parameters():
                 prm.requires_grad = False
             self.set_weights(weights)
-        num_sample = 0
-        loss = None
-        for _ in range(train_steps):  # moon.py:76-97
-            x, y = self.next_batch()
-            num_sample += x.shape[0]
-            self.optimizer.zero_grad()
-            _, pro1, y_pred = self.model(x, return_all=True)
-            loss = self.loss_fn(y_pred, y)
-            _, pro2, _ = self.global_model(x, return_all=True)
-            logits = self.model.cosine_similarity_fn(pro1, pro2).reshape(-1, 1)
-            for pre in self.prev_model_list:
-                _, pro3, _ = pre(x, return_all=True)
-                nega = self.model.cosine_similarity_fn(pro1, pro3)
-                logits = torch.cat((logits, nega.reshape(-1, 1)), dim=1)
-            logits = logits / self.model.temperature
-            labels = torch.zeros(x.size(0), dtype=torch.long, device=x.device)
-            loss = loss + self.model.mu * self.loss_fn(logits, labels)
-            loss.backward()
-            self.optimizer.step()
-        self.last_loss = float(loss.item()) if loss is not None else float("nan")
-        model_weights = self.get_weights(return_numpy=True)
-        if dp_strategy is not None and dp_strategy.model_gdp is not None:
-            model_weights = dp_strategy.model_gdp(model_weights)
+        num_sample = self._train(train_steps)
+        model_weights = self._model_gdp(self.get_weights(return_numpy=True), dp_strategy)
         # moon.py:115-130: keep the last model_buffer_size local models, frozen
         if len(self.prev_model_list) >= self.model_buffer_size:
             self.prev_model_list.pop(0)
@@ -273,26 +288,13 @@ class FedAvgU(FedAvgW):
 
     def train_step(self, updates, cur_steps: int, train_steps: int, refresh_data: bool = False,
                    dp_strategy=None, **kwargs):
-        self.model.train()
-        if refresh_data:
-            self._reset_data_iter()
+        self._begin_step(refresh_data)
         if updates is not None:  # fed_avg_u.py:55-57
             self.set_weights([np.add(w, u) for w, u in zip(self.get_weights(), updates)])
         old = self.get_weights()
-        num_sample = 0
-        loss = None
-        for _ in range(train_steps):
-            x, y = self.next_batch()
-            num_sample += x.shape[0]
-            self.optimizer.zero_grad()
-            loss = self.loss_fn(self.model(x), y)
-            loss.backward()
-            self.optimizer.step()
-        self.last_loss = float(loss.item()) if loss is not None else float("nan")
+        num_sample = self._train(train_steps)
         client_updates = [np.subtract(n, o) for n, o in zip(self.get_weights(), old)]  # :77-80
-        if dp_strategy is not None and dp_strategy.model_gdp is not None:
-            client_updates = dp_strategy.model_gdp(client_updates)
-        return client_updates, num_sample
+        return self._model_gdp(client_updates, dp_strategy), num_sample
 
     def apply_weights(self, updates, **kwargs):
         if updates is not None:
@@ -318,30 +320,26 @@ class FedAvgG(FedAvgW):
             if g is not None:
                 prm.grad = torch.from_numpy(np.array(g, copy=True)).to(device=prm.device, dtype=prm.dtype)
 
+    def _train_batch(self, x, y):
+        """No optimizer step: the batch's gradients join the round's payload."""
+        self.optimizer.zero_grad()
+        loss = self._loss(x, y)
+        loss.backward()
+        grads = [None if prm.grad is None else _host_array(prm.grad)
+                 for prm in self.model.parameters()]  # mixins.py:91-97
+        # list += list: concatenation (:91)
+        self._grad_sum = grads if self._grad_sum is None else self._grad_sum + grads
+        return loss
+
     def train_step(self, gradients, cur_steps: int, train_steps: int, refresh_data: bool = False,
                    dp_strategy=None, **kwargs):
-        self.model.train()
-        if refresh_data:
-            self._reset_data_iter()
+        self._begin_step(refresh_data)
         if gradients is not None:  # fed_avg_g.py:67-71
             self._set_gradients(gradients)
             self.optimizer.step()
-        num_sample = 0
-        loss = None
-        grad_sum = None
-        for _ in range(train_steps):
-            self.optimizer.zero_grad()
-            x, y = self.next_batch()
-            num_sample += x.shape[0]
-            loss = self.loss_fn(self.model(x), y)
-            loss.backward()
-            grads = [None if prm.grad is None else _host_array(prm.grad)
-                     for prm in self.model.parameters()]  # mixins.py:91-97
-            grad_sum = grads if grad_sum is None else grad_sum + grads  # list += list: concatenation (:91)
-        self.last_loss = float(loss.item()) if loss is not None else float("nan")
-        if dp_strategy is not None and dp_strategy.model_gdp is not None:
-            grad_sum = dp_strategy.model_gdp(grad_sum)
-        return grad_sum, num_sample
+        self._grad_sum = None
+        num_sample = self._train(train_steps)
+        return self._model_gdp(self._grad_sum, dp_strategy), num_sample
 
     def apply_weights(self, gradients, **kwargs):
         if gradients is not None:  # fed_avg_g.py:103-112
@@ -393,52 +391,36 @@ class FedSTC(FedAvgW):
     def _upload(self, payload: list) -> list:
         """What leaves the worker: with ``sparse_transport="both"`` the COO
         form of the payload (fed_stc.py:128)."""
-        if self.sparse_transport != "both":
-            return payload
-        from ..utils.compressor import sparse_encode
-
-        return sparse_encode(payload)
+        return sparse_encode(payload) if self.sparse_transport == "both" else payload
 
     @staticmethod
     def _dense(updates):
         """The downstream update, decoded if it came in COO form (fed_stc.py:71, :141)."""
-        from ..utils.sparse import SparseCOO, sparse_decode
-
         if updates is not None and any(isinstance(u, SparseCOO) for u in updates):
             return sparse_decode(updates)
         return updates
 
+    def _step(self, a, b, r):
+        """The strategy's compression of ``(a - b) + r`` where the operands live: (payload, residual)."""
+        return stc_step(a, b, r, self.sparsity)[:2]
+
     def _compress(self, a, b, r):
         """One layer's (payload, residual).  Float layers run on
         ``compress_device``; integer entries take the numpy path."""
-        from ..utils.compressor import stc_step
-
         if self._resident or self.compress_device.type == "cpu" or a.dtype not in (np.float32, np.float64):
-            sparse, res, _ = stc_step(a, b, r, self.sparsity)
-            return sparse, res
+            return self._step(a, b, r)
         dev = self.compress_device
-        sparse, res, _ = stc_step(H.h2d(a, dev), None if b is None else H.h2d(b, dev), r, self.sparsity)
+        sparse, res = self._step(H.h2d(a, dev), None if b is None else H.h2d(b, dev), r)
         return H.d2h(sparse, pooled=False), res
 
     def train_step(self, updates, cur_steps: int, train_steps: int, refresh_data: bool = False,
                    dp_strategy=None, **kwargs):
-        self.model.train()
-        if refresh_data:
-            self._reset_data_iter()
+        self._begin_step(refresh_data)
         updates = self._dense(updates)
         if updates is not None:  # fed_stc.py:69-73
             self.set_weights(self._plus(self.model_weights, updates))
         self.model_weights = self._state()  # :78
-        num_sample = 0
-        loss = None
-        for _ in range(train_steps):
-            x, y = self.next_batch()
-            num_sample += x.shape[0]
-            self.optimizer.zero_grad()
-            loss = self.loss_fn(self.model(x), y)
-            loss.backward()
-            self.optimizer.step()
-        self.last_loss = float(loss.item()) if loss is not None else float("nan")
+        num_sample = self._train(train_steps)
         new = self._state()
         res = self._res or [None] * len(new)
         if dp_strategy is not None and dp_strategy.model_gdp is not None:  # :113-118: DP on the dense update
@@ -485,15 +467,8 @@ class FedSCR(FedSTC):
         self.threshold = float(threshold)
         self.keep_residual = bool(keep_residual)
 
-    def _compress(self, a, b, r):
-        from ..utils.compressor import scr_step
-
-        if self._resident or self.compress_device.type == "cpu" or a.dtype not in (np.float32, np.float64):
-            return scr_step(a, b, r, self.threshold, want_res=self.keep_residual)
-        dev = self.compress_device
-        sparse, res = scr_step(H.h2d(a, dev), None if b is None else H.h2d(b, dev), r, self.threshold,
-                               want_res=self.keep_residual)
-        return H.d2h(sparse, pooled=False), res
+    def _step(self, a, b, r):
+        return scr_step(a, b, r, self.threshold, want_res=self.keep_residual)
 
     def train_step(self, updates, cur_steps: int, train_steps: int, refresh_data: bool = False,
                    dp_strategy=None, **kwargs):
@@ -568,6 +543,30 @@ class FLModel:
             w.set_weights(reveal(init.to(d)))
         return init
 
+    def _server_stc(self, agg_data: list):
+        """The ``fed_stc`` server step (fl_model.py:542-556, compress.py:28-42):
+        the server adds its residual to the aggregated update, compresses it,
+        keeps the new residual and adds the result to ``server_weight``, its
+        own copy of the model.  Gives (the sparse update, what goes back to
+        the parties: the same, or its COO form with ``sparse_transport``,
+        fl_model.py:558-563)."""
+        if isinstance(agg_data[0], torch.Tensor) and agg_data[0].is_cuda and \
+                not isinstance(self.server_weight[0], torch.Tensor):
+            # device payloads: the server's copy follows the aggregate onto its device
+            self.server_weight = [H.h2d(w, a.device) for w, a in zip(self.server_weight, agg_data)]
+        # a plain aggregator's unweighted initial average keeps the model's float32 while
+        # its weighted averages are float64 (numpy's promotion): the server's copy follows
+        # the aggregate's type too (a no-op with an aggregator whose results are all float64)
+        self.server_weight = [w if w.dtype == a.dtype else
+                              (w.to(a.dtype) if isinstance(w, torch.Tensor) else w.astype(a.dtype))
+                              for w, a in zip(self.server_weight, agg_data)]
+        res = self._res or [None] * len(agg_data)
+        steps_out = [stc_step(a, None, r, self._sparsity, acc=w)
+                     for a, r, w in zip(agg_data, res, self.server_weight)]
+        self._res = [s[1] for s in steps_out]
+        sparse = [s[0] for s in steps_out]
+        return sparse, (sparse_encode(sparse) if self.sparse_transport is not None else sparse)
+
     def fit(self, x: Dict[PYU, np.ndarray], y: Dict[PYU, np.ndarray], batch_size: int = 32, epochs: int = 1,
             aggregate_freq: int = 1, validation_data=None, round_hook: Callable | None = None) -> dict:
         """``round_hook(round_index, aggregated_params)`` is called after every
@@ -579,8 +578,6 @@ class FLModel:
         history = {"train_loss": [], "val_loss": [], "val_accuracy": [], "aggregation_s": [], "round_s": [],
                    "init_s": 0.0, "eval_s": 0.0}
         if self.sparse_transport is not None:
-            from ..utils.sparse import payload_nbytes, sparse_encode
-
             history["upload_bytes"], history["download_bytes"] = [], []
         # reference fit (fl_model.py:473): the initial weights are averaged
         # through the aggregator before the first epoch
@@ -589,10 +586,9 @@ class FLModel:
         history["init_s"] = time.perf_counter() - t_init
         if round_hook is not None:
             round_hook(-1, reveal(init))
-        server_weight = None
         if self.strategy == "fed_stc":  # fl_model.py:475-477: the server's copy of the model
-            server_weight = [w.detach().clone() if isinstance(w, torch.Tensor) else np.array(w, copy=True)
-                             for w in reveal(init)]
+            self.server_weight = [w.detach().clone() if isinstance(w, torch.Tensor) else np.array(w, copy=True)
+                                  for w in reveal(init)]
         rnd = 0
         for epoch in range(epochs):
             model_params_list = None
@@ -614,32 +610,9 @@ class FLModel:
                 if isinstance(agg_data, list) and agg_data and isinstance(agg_data[0], torch.Tensor):
                     torch.cuda.synchronize()
                 history["aggregation_s"].append(time.perf_counter() - t_agg)
-                if server_weight is not None:
-                    # fl_model.py:542-556, compress.py:28-42: the server adds its residual to the
-                    # aggregated update, compresses it, keeps the new residual and its own weights;
-                    # the sparse update is what goes back to the parties
-                    from ..utils.compressor import stc_step
-
-                    if isinstance(agg_data[0], torch.Tensor) and agg_data[0].is_cuda and \
-                            not isinstance(server_weight[0], torch.Tensor):
-                        # device payloads: the server's copy follows the aggregate onto its device
-                        server_weight = [H.h2d(w, a.device) for w, a in zip(server_weight, agg_data)]
-                    # a plain aggregator's unweighted initial average keeps the model's float32 while
-                    # its weighted averages are float64 (numpy's promotion): the server's copy follows
-                    # the aggregate's type too (a no-op with an aggregator whose results are all float64)
-                    server_weight = [w if w.dtype == a.dtype else
-                                     (w.to(a.dtype) if isinstance(w, torch.Tensor) else w.astype(a.dtype))
-                                     for w, a in zip(server_weight, agg_data)]
-                    res = self._res or [None] * len(agg_data)
-                    steps_out = [stc_step(a, None, r, self._sparsity, acc=w)
-                                 for a, r, w in zip(agg_data, res, server_weight)]
-                    self._res = [s[1] for s in steps_out]
-                    agg_data = [s[0] for s in steps_out]
-                    down = agg_data
-                    if self.sparse_transport is not None:  # fl_model.py:558-563
-                        down = sparse_encode(agg_data)
+                if self.strategy == "fed_stc":
+                    agg_data, down = self._server_stc(agg_data)
                     model_params = PYUObject(model_params.device, down)
-                    self.server_weight = server_weight
                 if self.sparse_transport is not None:
                     history["download_bytes"].append(len(self.device_list) * payload_nbytes(reveal(model_params)))
                 model_params_list = [model_params.to(d) for d in self.device_list]

@@ -70,19 +70,57 @@ def _stc_numpy(u: np.ndarray, mask_num: int):
         return mu * np.sign(um), mu
 
 
-def _scratch_for(t: torch.Tensor) -> torch.Tensor:
-    """The device's scratch for the current stream, grown on demand."""
+def _scratch_for(t: torch.Tensor, need_bytes: int) -> torch.Tensor:
+    """The device's scratch for the current stream, grown on demand.  STC and
+    SCR share it: calls on a stream are ordered."""
     from .. import kernels as K
 
-    need = K.stc_scratch_bytes(t.numel(), t.dtype)
     key = (t.device.index, K._stream(t))
     s = _scratch.get(key)
-    if s is None or s.numel() < need:
-        s = _scratch[key] = torch.empty(need, dtype=torch.uint8, device=t.device)
+    if s is None or s.numel() < need_bytes:
+        s = _scratch[key] = torch.empty(need_bytes, dtype=torch.uint8, device=t.device)
     return s
 
 
-def _step_device(a, b, r, sparse_rate, acc):
+def _form_host(a, b, r) -> np.ndarray:
+    """``u = (a - b) + r`` in numpy; an absent ``b`` or ``r`` is skipped."""
+    u = np.asarray(a)
+    if b is not None:
+        u = np.subtract(u, np.asarray(b))
+    if r is not None:
+        u = np.add(u, np.asarray(r))
+    return u
+
+
+def _run_where_it_lives(who: str, device_fn, host_fn, a, b, r, acc=None):
+    """One step on ``(a, b, r, acc)`` where ``a`` lives.  CUDA float32 /
+    float64 tensors go to ``device_fn``; everything else goes to ``host_fn``
+    as numpy arrays, and the first two results (``sparse``, ``res`` or None)
+    come back as what ``a`` was: CUDA integer entries cross pinned memory both
+    ways (``acc`` is written back), CPU tensors are viewed (``acc`` in place),
+    numpy stays numpy.  Further results (``mu``) pass as ``host_fn`` gave them."""
+    ops = (a, b, r, acc)
+    if not isinstance(a, torch.Tensor):
+        return host_fn(*ops)
+    if a.is_cuda and a.dtype in (torch.float32, torch.float64):
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ops if t is not None):
+            raise ValueError(f"{who}: every operand of a device step is a device tensor")
+        return device_fn(*ops)
+    if a.is_cuda:  # integer state entries: the numpy path, across pinned memory
+        from .. import hostpipe as H
+
+        host = [None if t is None else H.d2h(t, pooled=False) for t in ops]
+        out = host_fn(*host)
+        if acc is not None:
+            acc.copy_(H.h2d(host[3], a.device))
+        back = lambda x: H.h2d(x, a.device)  # noqa: E731
+    else:
+        out = host_fn(*(None if t is None else t.detach().numpy() for t in ops))  # views: acc in place
+        back = torch.from_numpy
+    return (*(None if x is None else back(x) for x in out[:2]), *out[2:])
+
+
+def _stc_device(a, b, r, acc, sparse_rate):
     from .. import kernels as K
 
     shape = a.shape
@@ -96,16 +134,13 @@ def _step_device(a, b, r, sparse_rate, acc):
         raise ValueError("stc_step: acc is a contiguous tensor of the data's dtype, shape and device")
     if n:
         K.stc(flat[0], flat[1], flat[2], mask_count(sparse_rate, n), sparse, res,
-              acc=None if acc is None else acc.detach().view(-1), mu_out=mu.view(1), scratch=_scratch_for(flat[0]))
+              acc=None if acc is None else acc.detach().view(-1), mu_out=mu.view(1),
+              scratch=_scratch_for(flat[0], K.stc_scratch_bytes(n, a.dtype)))
     return sparse.view(shape), res.view(shape), mu
 
 
-def _step_host(a, b, r, sparse_rate, acc):
-    u = np.asarray(a)
-    if b is not None:
-        u = np.subtract(u, np.asarray(b))
-    if r is not None:
-        u = np.add(u, np.asarray(r))
+def _stc_host(a, b, r, acc, sparse_rate):
+    u = _form_host(a, b, r)
     if u.dtype not in _KEY:  # integer state entries: float64, as numpy's mean * sign promotes them
         u = u.astype(np.float64)
     shape = u.shape
@@ -130,24 +165,8 @@ def stc_step(a, b, r, sparse_rate: float, acc=None):
     tensor: nothing is synchronised); numpy arrays give numpy arrays and CPU
     tensors CPU tensors, through the numpy implementation."""
     _check_rate(sparse_rate)
-    ts = [t for t in (a, b, r, acc) if t is not None]
-    if isinstance(a, torch.Tensor):
-        if a.is_cuda and a.dtype in (torch.float32, torch.float64):
-            if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
-                raise ValueError("stc_step: every operand of a device step is a device tensor")
-            return _step_device(a, b, r, sparse_rate, acc)
-        if a.is_cuda:  # integer state entries: the numpy path, across pinned memory
-            from .. import hostpipe as H
-
-            host = [None if t is None else H.d2h(t, pooled=False) for t in (a, b, r, acc)]
-            sparse, res, mu = _step_host(*host[:3], sparse_rate, host[3])
-            if acc is not None:
-                acc.copy_(H.h2d(host[3], a.device))
-            return H.h2d(sparse, a.device), H.h2d(res, a.device), mu
-        host = [None if t is None else t.detach().numpy() for t in (a, b, r, acc)]  # views: acc in place
-        sparse, res, mu = _step_host(*host[:3], sparse_rate, host[3])
-        return torch.from_numpy(sparse), torch.from_numpy(res), mu
-    return _step_host(a, b, r, sparse_rate, acc)
+    return _run_where_it_lives("stc_step", lambda *ops: _stc_device(*ops, sparse_rate),
+                               lambda *ops: _stc_host(*ops, sparse_rate), a, b, r, acc)
 
 
 class STCSparse:
@@ -182,11 +201,7 @@ def _scr_drops(mag: np.ndarray, threshold: float) -> np.ndarray:
 
 
 def _scr_host(a, b, r, threshold, want_res):
-    u = np.asarray(a)
-    if b is not None:
-        u = np.subtract(u, np.asarray(b))
-    if r is not None:
-        u = np.add(u, np.asarray(r))
+    u = _form_host(a, b, r)
     sparse = np.array(u, copy=True, order="C")  # the inputs stay as they are
     v3 = _view3(u.shape)
     if v3 is not None and u.size:
@@ -200,19 +215,6 @@ def _scr_host(a, b, r, threshold, want_res):
         return sparse, None
     with np.errstate(invalid="ignore"):
         return sparse, np.subtract(u, sparse)
-
-
-def _scr_scratch_for(t: torch.Tensor, v3) -> torch.Tensor:
-    """The current stream's scratch (the one STC uses: calls on a stream are
-    ordered), grown to what SCR needs for the shape."""
-    from .. import kernels as K
-
-    need = K.scr_scratch_bytes(v3, t.dtype)
-    key = (t.device.index, K._stream(t))
-    s = _scratch.get(key)
-    if s is None or s.numel() < need:
-        s = _scratch[key] = torch.empty(need, dtype=torch.uint8, device=t.device)
-    return s
 
 
 def _scr_device(a, b, r, threshold, want_res):
@@ -231,7 +233,8 @@ def _scr_device(a, b, r, threshold, want_res):
     sparse = torch.empty_like(flat[0])
     res = torch.empty_like(flat[0]) if want_res else None
     if sparse.numel():
-        K.scr(flat[0], flat[1], flat[2], v3, threshold, sparse, res, scratch=_scr_scratch_for(flat[0], v3))
+        K.scr(flat[0], flat[1], flat[2], v3, threshold, sparse, res,
+              scratch=_scratch_for(flat[0], K.scr_scratch_bytes(v3, a.dtype)))
     return sparse.view(shape), (res.view(shape) if want_res else None)
 
 
@@ -265,21 +268,8 @@ def scr_step(a, b, r, threshold: float, want_res: bool = True):
     integer entries run numpy; integer results stay in their own dtype.  Host
     and device add the sums in different orders (about 1e-13 relative), which
     matters only for a ratio that close to the threshold."""
-    ts = [t for t in (a, b, r) if t is not None]
-    if isinstance(a, torch.Tensor):
-        if a.is_cuda and a.dtype in (torch.float32, torch.float64):
-            if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
-                raise ValueError("scr_step: every operand of a device step is a device tensor")
-            return _scr_device(a, b, r, threshold, want_res)
-        if a.is_cuda:  # integer state entries: the numpy path, across pinned memory
-            from .. import hostpipe as H
-
-            sparse, res = _scr_host(*(None if t is None else H.d2h(t, pooled=False) for t in (a, b, r)),
-                                    threshold, want_res)
-            return H.h2d(sparse, a.device), (H.h2d(res, a.device) if want_res else None)
-        sparse, res = _scr_host(*(None if t is None else t.detach().numpy() for t in (a, b, r)), threshold, want_res)
-        return torch.from_numpy(sparse), (torch.from_numpy(res) if want_res else None)
-    return _scr_host(a, b, r, threshold, want_res)
+    return _run_where_it_lives("scr_step", lambda a, b, r, _: _scr_device(a, b, r, threshold, want_res),
+                               lambda a, b, r, _: _scr_host(a, b, r, threshold, want_res), a, b, r)
 
 
 class SCRSparse:

@@ -16,10 +16,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import scr_oracle as so  # noqa: E402
+from gpu_copies import DEV, _bits, _dev, _host  # noqa: E402
 from test_scr_oracle import DECISIVE, DECISIVE_IDS, THR, TIES, decisive, specials  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 IDS = ["f32", "f64"]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scr_reference.npz")
 # Beside the fixture's shapes, for the operand forms: float32 rows that are a
@@ -45,32 +45,6 @@ def _gpu():
 @pytest.fixture(scope="module")
 def golden():
     return np.load(GOLDEN)
-
-
-def _bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.uint32 if x.dtype == np.float32 else np.uint64)
-
-
-def _dev(x, misalign=False):
-    """On the device through hostpipe's pinned copies, like the product: no
-    pageable DMA in a process that may hold registered host memory."""
-    from sfl_amd import hostpipe as H
-
-    if x is None:
-        return None
-    flat = H.h2d(np.ascontiguousarray(x).reshape(-1), torch.device(DEV))
-    if not misalign:
-        return flat
-    t = torch.empty(flat.numel() + 1, dtype=flat.dtype, device=DEV)  # element-aligned only
-    t[1:].copy_(flat)
-    return t[1:]
-
-
-def _host(t):
-    from sfl_amd import hostpipe as H
-
-    return H.d2h(t, pooled=False)
 
 
 def run(a, b=None, r=None, thr=0.0, want_res=True, alias=False, misalign=False, fill=None, stats=True):

@@ -6,9 +6,9 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import stc_oracle as so  # noqa: E402
+from gpu_copies import DEV, _bits, _dev, _host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 N = (1, 2, 63, 64, 65, 255, 256, 257, 4099, 65537, 2**20 + 3)
 RATES = (0.0, 0.5, 0.9, 0.99, 1.0)
 DTYPES = (np.float32, np.float64)
@@ -24,20 +24,6 @@ def _gpu():
         pytest.skip("no GPU")
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32 if x.dtype == np.float32 else np.uint64)
-
-
-def _dev(x, misalign=False):
-    if x is None:
-        return None
-    if not misalign:
-        return torch.from_numpy(x).to(DEV)
-    t = torch.empty(x.size + 1, dtype=torch.from_numpy(x).dtype, device=DEV)  # element-aligned only
-    t[1:].copy_(torch.from_numpy(x))
-    return t[1:]
-
-
 def run(a, b=None, r=None, m=0, acc=None, alias=False, misalign=False, want_mu=True):
     """(sparse, res, mu, acc') as host arrays."""
     from sfl_amd import kernels as K
@@ -49,8 +35,8 @@ def run(a, b=None, r=None, m=0, acc=None, alias=False, misalign=False, want_mu=T
     scratch = torch.empty(K.stc_scratch_bytes(a.size, ta.dtype), dtype=torch.uint8, device=DEV)
     K.stc(ta, tb, tr, m, sparse, res, acc=tacc, mu_out=mu, scratch=scratch)
     torch.cuda.synchronize()
-    return (sparse.cpu().numpy(), res.cpu().numpy(), None if mu is None else mu.cpu().numpy()[0],
-            None if acc is None else tacc.cpu().numpy())
+    return (_host(sparse), _host(res), None if mu is None else _host(mu)[0],
+            None if acc is None else _host(tacc))
 
 
 def check(a, b, r, m, acc, out):
@@ -211,14 +197,13 @@ def test_compressor_takes_the_device_path():
     from sfl_amd.utils import compressor as Cz
 
     a, b, r, acc = (x.reshape(4099, 1) for x in _case(np.float32, 4099))
-    tacc = _dev(acc.copy())
-    sparse, res, mu = Cz.stc_step(_dev(a), _dev(b), _dev(r), 0.9, acc=tacc)
+    tacc = _dev(acc).view(acc.shape)
+    sparse, res, mu = Cz.stc_step(*(_dev(x).view(a.shape) for x in (a, b, r)), 0.9, acc=tacc)
     assert sparse.is_cuda and res.is_cuda and mu.is_cuda and sparse.shape == a.shape
     m = so.mask_count(0.9, a.size)
-    out = (sparse.cpu().numpy().reshape(-1), res.cpu().numpy().reshape(-1), mu.cpu().numpy()[()],
-           tacc.cpu().numpy().reshape(-1))
+    out = (_host(sparse).reshape(-1), _host(res).reshape(-1), _host(mu)[()], _host(tacc).reshape(-1))
     check(a.reshape(-1), b.reshape(-1), r.reshape(-1), m, acc.reshape(-1), out)
-    (again,) = Cz.STCSparse(0.9)([_dev(so.form(a, b, r))])
+    (again,) = Cz.STCSparse(0.9)([_dev(so.form(a, b, r)).view(a.shape)])
     assert torch.equal(again, sparse)
 
 
