@@ -480,6 +480,75 @@ int sa_scr_scratch_bytes(uint64_t rows, uint64_t cols, uint64_t inner, int x_typ
 int sa_scr(const void* a, const void* b, const void* r, int x_type, uint64_t rows, uint64_t cols, uint64_t inner,
            double threshold, void* sparse_out, void* res_out, void* stats_out, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* GaussianModelDP with is_secure_generator (mechanism_fl.py:112-127    */
+/* drawing from sfl/security/random/distrbutions.py:89-137): the same   */
+/* clip as sa_dp_perturb_f32, the noise from a cryptographic generator  */
+/* and combined as Holohan and Braghin describe (arXiv:2107.10138).     */
+/* The reference takes its uniforms from the OS CSPRNG; here they are   */
+/* a keyed ChaCha20 keystream, so the noise is reproducible from        */
+/* (key, nonce, counter) and parallel over the elements.                */
+/*                                                                      */
+/* Keystream: ChaCha20 as in RFC 8439 section 2.3 (20 rounds, the input */
+/* state added at the end).  State words 0-3: the constants 61707865    */
+/* 3320646e 79622d32 6b206574; 4-11: the 256-bit key as eight           */
+/* little-endian words; 12, 13: the low and high halves of a 64-bit     */
+/* block counter B; 14, 15: the low and high halves of a 64-bit nonce.  */
+/* (With word 13 read as the RFC's first nonce word this is the RFC's   */
+/* layout: its test vector 2.3.2 is B = 0x0900000000000001, nonce       */
+/* 0x4a000000.)  The output words are o[0..15].                         */
+/*                                                                      */
+/* Noise index i = counter0 + e (counter0 % 4 == 0) uses block B = i>>2 */
+/* and j = i & 3; a, b, c, d = o[4j .. 4j+3] give two 53-bit uniforms   */
+/* (the reference's secrets.randbits(53) / 2**53), all in float64:      */
+/*   u1 = (((b << 32) | a) >> 11) * 2^-53                               */
+/*   u2 = (((d << 32) | c) >> 11) * 2^-53                               */
+/*   r  = sqrt(-2.0 * log(1.0 - u2))      theta = (2.0 * pi) * u1       */
+/*   z64 = ((r * sin(theta)) * sigma + (r * cos(theta)) * sigma)        */
+/*         / sqrt(2.0)                                                  */
+/* in the reference's operation order (u1 drawn first, feeding theta;   */
+/* sigma multiplies each Box-Muller output before they are summed);     */
+/* 1 - u2 lies in (0, 1], so no draw is infinite.  Then                 */
+/*   z32 = (float) z64                    (the reference's astype)      */
+/*   x'  = fl32(x * scale) + fl32(z32 / num_updates)                    */
+/* with the scale of sa_dp_perturb_f32.  No multiply-add is fused.      */
+/* A (key, nonce, counter) triple must never be used twice: the caller  */
+/* advances counter0 by whole blocks and draws fresh keys from the OS.  */
+/* sa_mask_dp has no secure form (it draws Philox noise): perturb       */
+/* first, then sa_mask.                                                 */
+/* ------------------------------------------------------------------ */
+
+typedef struct sa_dp_secure {
+  const double* sumsq;       /* device: the clipping group's squared norm (sa_sumsq_f32) */
+  const double* sumsq_layer; /* device, optional: this layer's squared norm */
+  double l2_norm_clip;
+  double noise_std;   /* sigma = noise_multiplier * clip * clip, a double */
+  float num_updates;  /* divisor of the noise (> 0) */
+  uint32_t key[8];    /* ChaCha20 key, little-endian words */
+  uint64_t nonce;
+  uint64_t counter0;  /* noise index of element 0 (multiple of 4) */
+} sa_dp_secure;
+
+/* out = clip-and-secure-noise(x) (out may alias x); 16-byte aligned x and out. */
+int sa_dp_perturb_secure_f32(const float* x, uint64_t n, const sa_dp_secure* dp, float* out, void* stream);
+
+/* The raw keystream on the device: out[16 k .. 16 k + 15] = block block0 + k
+ * (the block counter wraps mod 2^64), k < n_blocks; out is 16-byte aligned
+ * device memory of 16 * n_blocks words. */
+int sa_chacha20_keystream(const uint32_t key[8], uint64_t nonce, uint64_t block0, uint64_t n_blocks, uint32_t* out,
+                          void* stream);
+
+/* The same blocks on the host (no GPU needed; `out` is host memory): the
+ * cipher's known-answer tests.  Not used by any hot-path entry point. */
+int sa_chacha20_blocks_host(const uint32_t key[8], uint64_t nonce, uint64_t block0, uint64_t n_blocks,
+                            uint32_t* out);
+
+/* The transform alone: out[i] = z64 of the words a, b, c, d = words[4 i ..
+ * 4 i + 3] (device memory) -- the function the perturb kernel calls, so
+ * its edge inputs (u2 = 0, sin + cos cancelling at u1 = 3/8, 7/8) can be
+ * reached, which no search of cipher blocks can. */
+int sa_hb_normals_f64(const uint32_t* words, uint64_t n, double sigma, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ EXPORTED = (
     "sa_comm_allreduce_u64", "sa_comm_reduce_scatter_u64", "sa_comm_alltoall_u64", "sa_comm_gather_f64", "sa_comm_info", "sa_comm_destroy", "sa_sumsq_f32", "sa_dp_perturb_f32", "sa_mask_dp",
     "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64", "sa_stc_scratch_bytes", "sa_stc",
     "sa_scr_scratch_bytes", "sa_scr",
+    "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
 )
 
 
@@ -77,6 +78,13 @@ class DP(C.Structure):
     _fields_ = [("sumsq", C.c_void_p), ("sumsq_layer", C.c_void_p), ("l2_norm_clip", C.c_double),
                 ("noise_std", C.c_float), ("num_updates", C.c_float),
                 ("key", C.c_uint64), ("counter0", C.c_uint64)]
+
+
+class DPSecure(C.Structure):
+    """sa_dp_secure: GaussianModelDP pre-step parameters with ChaCha20 noise."""
+    _fields_ = [("sumsq", C.c_void_p), ("sumsq_layer", C.c_void_p), ("l2_norm_clip", C.c_double),
+                ("noise_std", C.c_double), ("num_updates", C.c_float), ("key", C.c_uint32 * 8),
+                ("nonce", C.c_uint64), ("counter0", C.c_uint64)]
 
 
 _lock = threading.Lock()
@@ -126,6 +134,10 @@ def _declare(lib):
     lib.sa_stc.argtypes = [vp, vp, vp, i32, u64, u64, vp, vp, vp, vp, vp, vp]
     lib.sa_scr_scratch_bytes.argtypes = [u64, u64, u64, i32]
     lib.sa_scr.argtypes = [vp, vp, vp, i32, u64, u64, u64, dbl, vp, vp, vp, vp, vp]
+    lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
+    lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
+    lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]
+    lib.sa_hb_normals_f64.argtypes = [vp, u64, dbl, vp, vp]
     for name in EXPORTED:
         if name not in ("sa_last_error",):
             getattr(lib, name).restype = i32
@@ -222,4 +234,23 @@ def pcg64_raw_host(g: PCG64, n: int):
     tmp = PCG64(g.state, g.inc)
     check(lib().sa_pcg64_raw_host(C.byref(tmp), out.ctypes.data_as(C.POINTER(C.c_uint64)), n),
           "sa_pcg64_raw_host")
+    return out
+
+
+def chacha_key_words(key: bytes) -> C.Array:
+    """A 32-byte ChaCha20 key as the eight little-endian words of sa_dp_secure."""
+    key = bytes(key)
+    if len(key) != 32:
+        raise ValueError(f"a ChaCha20 key has 32 bytes, not {len(key)}")
+    return (C.c_uint32 * 8)(*[int.from_bytes(key[4 * i:4 * i + 4], "little") for i in range(8)])
+
+
+def chacha20_blocks_host(key: bytes, nonce: int, block0: int, n_blocks: int):
+    """ChaCha20 blocks block0 .. block0 + n_blocks - 1 as (n_blocks, 16) uint32, computed on the host."""
+    import numpy as np
+
+    out = np.empty((n_blocks, 16), dtype=np.uint32)
+    m = (1 << 64) - 1
+    check(lib().sa_chacha20_blocks_host(chacha_key_words(key), int(nonce) & m, int(block0) & m, n_blocks,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint32))), "sa_chacha20_blocks_host")
     return out

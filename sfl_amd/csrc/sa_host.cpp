@@ -16,6 +16,7 @@
 
 #include "../../include/sfl_sa.h"
 #include "pcg128.h"
+#include "sa_chacha.h"
 #include "sa_internal.h"
 
 namespace {
@@ -143,5 +144,17 @@ extern "C" int sa_pcg64_raw_host(sa_pcg64* g, uint64_t* out, uint64_t n) {
     out[i] = sa::xslrr(s);
   }
   g->state = from128(s);
+  return SA_OK;
+}
+
+// The ChaCha20 blocks of sa_chacha20_keystream on the host (sa_chacha.h's
+// block function compiled for the CPU): the cipher's known-answer tests.
+extern "C" int sa_chacha20_blocks_host(const uint32_t key[8], uint64_t nonce, uint64_t block0, uint64_t n_blocks,
+                                       uint32_t* out) {
+  if (!key || (n_blocks && !out)) {
+    sa_set_error("sa_chacha20_blocks_host: bad arguments");
+    return SA_ERR_ARG;
+  }
+  for (uint64_t b = 0; b < n_blocks; b++) sa::chacha20_block(key, nonce, block0 + b, out + 16 * b);
   return SA_OK;
 }

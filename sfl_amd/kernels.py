@@ -440,6 +440,61 @@ def mask_dp(x: torch.Tensor, out: torch.Tensor, streams: Sequence[tuple], dp: L.
 
 
 # ---------------------------------------------------------------------------
+# GaussianModelDP with ChaCha20 noise (sa_dp_perturb_secure_f32 and the two
+# halves it is made of: sa_chacha20_keystream, sa_hb_normals_f64).  uint32
+# words are carried as ``torch.int32`` tensors (same bits).
+# ---------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def make_dp_secure(sumsq: torch.Tensor, *, l2_norm_clip: float, noise_std: float, num_updates: float, key: bytes,
+                   nonce: int, counter0: int = 0, sumsq_layer: torch.Tensor | None = None) -> L.DPSecure:
+    if counter0 % 4:
+        raise ValueError("counter0 must be a multiple of 4")
+    d = L.DPSecure()
+    d.sumsq = sumsq.data_ptr()
+    d.sumsq_layer = sumsq_layer.data_ptr() if sumsq_layer is not None else None
+    d.l2_norm_clip = float(l2_norm_clip)
+    d.noise_std = float(noise_std)
+    d.num_updates = float(num_updates)
+    d.key = L.chacha_key_words(key)
+    d.nonce = int(nonce) & _M64
+    d.counter0 = int(counter0)
+    return d
+
+
+def dp_perturb_secure(x: torch.Tensor, out: torch.Tensor, dp: L.DPSecure) -> torch.Tensor:
+    _require_gpu(x, out)
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() != x.numel():
+        raise ValueError("dp_perturb_secure: float32 x and out of equal size")
+    L.check(L.lib().sa_dp_perturb_secure_f32(_ptr(x), x.numel(), C.byref(dp), _ptr(out), C.c_void_p(_stream(out))),
+            "sa_dp_perturb_secure_f32")
+    return out
+
+
+def chacha20_keystream(key: bytes, nonce: int, block0: int, out: torch.Tensor) -> torch.Tensor:
+    """out (int32, 16 words per block) = the ChaCha20 blocks block0 .. of (key, nonce)."""
+    _require_gpu(out)
+    if out.dtype != torch.int32 or out.numel() % 16:
+        raise ValueError("chacha20_keystream: an int32 out of 16 words per block")
+    L.check(L.lib().sa_chacha20_keystream(L.chacha_key_words(key), int(nonce) & _M64, int(block0) & _M64,
+                                          out.numel() // 16, _ptr(out), C.c_void_p(_stream(out))),
+            "sa_chacha20_keystream")
+    return out
+
+
+def hb_normals(words: torch.Tensor, sigma: float, out: torch.Tensor) -> torch.Tensor:
+    """out[i] (float64) = the normal of standard deviation sigma that the four
+    words words[4 i .. 4 i + 3] (int32) make (sa_hb_normals_f64)."""
+    _require_gpu(words, out)
+    if words.dtype != torch.int32 or out.dtype != torch.float64 or words.numel() != 4 * out.numel():
+        raise ValueError("hb_normals: int32 words, four per float64 element of out")
+    L.check(L.lib().sa_hb_normals_f64(_ptr(words), out.numel(), float(sigma), _ptr(out), C.c_void_p(_stream(out))),
+            "sa_hb_normals_f64")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # sparse ternary compression (sa_stc; fed_stc's worker and server halves)
 # ---------------------------------------------------------------------------
 def stc_scratch_bytes(n: int, dtype: torch.dtype) -> int:

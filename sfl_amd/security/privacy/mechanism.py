@@ -20,6 +20,11 @@ The noise is Philox4x32-10 + Box-Muller keyed by a 64-bit key and the
 element index (reproducible, parallel), not numpy's unseeded global
 ``np.random.normal`` stream; the privacy accounting (RDP) is unchanged by
 that and is out of scope here.
+
+``SecureGaussianModelDP`` is the reference's ``is_secure_generator=True``:
+the same clip, the noise from a ChaCha20 keystream and ``SecureNormalReal``'s
+float64 transform (``sa_dp_perturb_secure_f32``), at about
+nine times the Philox kernel's time.
 """
 
 from __future__ import annotations
@@ -40,7 +45,8 @@ class GaussianModelDP:
                  l2_norm_clip: float = 1.0, delta: Optional[float] = None, is_secure_generator: bool = False,
                  is_clip_each_layer: bool = False, *, device=None, seed: Optional[int] = None) -> None:
         if is_secure_generator:
-            raise NotImplementedError("is_secure_generator: this build draws noise from Philox4x32-10 only")
+            raise NotImplementedError("is_secure_generator: this class draws noise from Philox4x32-10 only; "
+                                      "SecureGaussianModelDP draws it from ChaCha20")
         self.noise_multiplier = noise_multiplier
         self.l2_norm_clip = l2_norm_clip
         self.num_clients = num_clients
@@ -80,6 +86,14 @@ class GaussianModelDP:
         self.counter += -(-n // 4) * 4
         return d
 
+    def _perturb(self, x: torch.Tensor, y: torch.Tensor, sumsq: torch.Tensor,
+                 sumsq_layer: torch.Tensor | None) -> torch.Tensor:
+        """y = clip + noise of the flat layer x; advances the noise counter."""
+        dp = self.params(sumsq, x.numel(), sumsq_layer)
+        if x.numel():
+            K.dp_perturb(x, y, dp)
+        return y
+
     def __call__(self, inputs: List):
         """Clip + noise every array of ``inputs``; numpy in -> numpy out,
         torch in -> torch (float32, on ``device``) out."""
@@ -96,11 +110,7 @@ class GaussianModelDP:
                 layer = torch.zeros(1, dtype=torch.float64, device=self.device)
                 if x.numel():
                     K.sumsq_f32(x, layer, part)
-            y = torch.empty_like(x)
-            dp = self.params(total, x.numel(), layer)
-            if x.numel():
-                K.dp_perturb(x, y, dp)
-            y = y.reshape(shape)
+            y = self._perturb(x, torch.empty_like(x), total, layer).reshape(shape)
             out.append(y if as_torch else H.d2h(y, pooled=False))
         return out
 
@@ -109,6 +119,52 @@ class GaussianModelDP:
         ``global_norm`` returns it under numpy 1.23.5 (mechanism_fl.py:132-135)."""
         xs = [self._flat(a) for a in inputs]
         return float(np.sqrt(np.float64(self.sumsq(xs).item())))
+
+
+class SecureGaussianModelDP(GaussianModelDP):
+    """``GaussianModelDP(..., is_secure_generator=True)`` of the reference
+    (mechanism_fl.py:112-127 over sfl/security/random's ``SecureNormalReal``):
+    the same clip, the noise from a cryptographic generator, two 53-bit
+    uniforms per normal and the Box-Muller pair combined as Holohan and
+    Braghin describe, in float64 (``sa_dp_perturb_secure_f32``; the
+    definition is in include/sfl_sa.h).  The reference reads the OS CSPRNG
+    element by element; here a ChaCha20 keystream under a 256-bit ``key``
+    and a 64-bit ``nonce``, both drawn from the OS CSPRNG by default, is
+    expanded on the GPU.
+
+    ``key`` (32 bytes) and ``nonce`` are arguments for tests only: noise
+    under a key anyone else knows, or a (key, nonce, counter) used twice,
+    protects nothing.  ``counter`` advances by whole ChaCha blocks per layer,
+    so no noise index is ever drawn twice under one instance.
+
+    ``sa_mask_dp`` draws Philox noise, so ``params()`` refuses: perturb with
+    ``__call__`` first, then mask."""
+
+    def __init__(self, noise_multiplier: float, num_clients: int, num_updates: Optional[int] = None,
+                 l2_norm_clip: float = 1.0, delta: Optional[float] = None, is_clip_each_layer: bool = False, *,
+                 device=None, key: Optional[bytes] = None, nonce: Optional[int] = None) -> None:
+        super().__init__(noise_multiplier, num_clients, num_updates, l2_norm_clip, delta,
+                         is_clip_each_layer=is_clip_each_layer, device=device, seed=0)
+        self.is_secure_generator = True
+        self.key = secrets.token_bytes(32) if key is None else bytes(key)
+        if len(self.key) != 32:
+            raise ValueError(f"key: a ChaCha20 key has 32 bytes, not {len(self.key)}")
+        self.nonce = secrets.randbits(64) if nonce is None else int(nonce)
+        if not 0 <= self.nonce < 1 << 64:
+            raise ValueError("nonce: a 64-bit unsigned integer")
+
+    def params(self, sumsq, n, sumsq_layer=None):
+        raise TypeError("SecureGaussianModelDP.params(): sa_mask_dp draws Philox noise, not ChaCha20; perturb the "
+                        "update with __call__ first and mask the result")
+
+    def _perturb(self, x, y, sumsq, sumsq_layer):
+        dp = K.make_dp_secure(sumsq, l2_norm_clip=self.l2_norm_clip, noise_std=self.noise_std,
+                              num_updates=self.num_updates, key=self.key, nonce=self.nonce, counter0=self.counter,
+                              sumsq_layer=sumsq_layer)
+        self.counter += -(-x.numel() // 4) * 4
+        if x.numel():
+            K.dp_perturb_secure(x, y, dp)
+        return y
 
 
 class DPStrategyFL:

@@ -13,7 +13,10 @@ against the masking it rides on, one client of --elems float32 elements:
 
 Median of --reps launches per pass (HIP events), the cases interleaved over
 --passes after a clock warm-up; one JSON line per case (median of the passes).
-usage: python tools/dp_bench.py [--elems 100000000] [--streams 7] [--reps 20] [--passes 3]
+--secure adds the ChaCha20 form of the standalone kernel (k_dp_perturb_secure,
+sfl_amd/csrc/sa_dp_secure.hip: one ChaCha20 block and four float64
+Holohan-Braghin normals per four elements), interleaved with the others.
+usage: python tools/dp_bench.py [--elems 100000000] [--streams 7] [--reps 20] [--passes 3] [--secure]
 """
 import argparse
 import json
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=30, help="lean masking launches before the first case")
+    ap.add_argument("--secure", action="store_true", help="also time sa_dp_perturb_secure_f32")
     args = ap.parse_args()
     import torch
 
@@ -74,6 +78,9 @@ def main():
         (f"dp_perturb then sa_mask, {args.streams} streams (unfused)", 20,
          lambda: (K.dp_perturb(x, xp, dp), K.mask(xp, out, streams))),
     ]
+    if args.secure:
+        dps = K.make_dp_secure(ss, l2_norm_clip=1.0, noise_std=0.5, num_updates=8.0, key=bytes(range(32)), nonce=7)
+        cases.insert(2, ("k_dp_perturb_secure (standalone, ChaCha20)", 8, lambda: K.dp_perturb_secure(x, xp, dps)))
     # warm the clocks, then interleave the cases over passes (the first
     # launches after idle run at lower clocks)
     for _ in range(args.warmup):
