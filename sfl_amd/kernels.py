@@ -638,3 +638,10 @@ def rejected_draws_many(gens: Sequence, n: int, device) -> list:
     further."""
     first = find_zero_draws(list(gens), n, device)
     return [rejected_draws(g, n, device, first=f) for g, f in zip(gens, first)]
+
+
+def stream_shifts(out: torch.Tensor, gen, sign: int, pts: Sequence[tuple]) -> torch.Tensor:
+    """``stream_shift`` at every (element, shift) point ``rejected_draws`` found on one stream."""
+    for k, shift in pts:
+        stream_shift(out, gen, sign, k, shift)
+    return out

@@ -28,7 +28,6 @@ spawned process per party.
 
 from __future__ import annotations
 
-import functools
 import os
 import threading
 from dataclasses import dataclass, field
@@ -36,17 +35,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .masker import Masker
-
-_F32, _F64, _I64 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
-def _torch_dtypes() -> dict:
-    """The three element / arithmetic types as torch dtypes (torch is imported on first use)."""
-    import torch
-
-    return {_F32: torch.float32, _F64: torch.float64, _I64: torch.int64}
-
+from .payload import (SMALL_CALL_BYTES, element_types, flat_host, host_weight, is_torch, np_dtype, scalar_weight,
+                      shape, split_layers, to_device, torch_dtypes)
 
 # the server's large sum_decode stages vectors that are not pooled results
 # (vectors deserialised from other processes) through the feeder; with
@@ -129,29 +119,6 @@ def agree(masker: Masker, peer_keys: dict, seeds: dict | None = None) -> Masker:
 
 
 # ------------------------------------------------------------- client side
-def _layers(payload):
-    if isinstance(payload, tuple):
-        return list(payload), "tuple"
-    if isinstance(payload, list):
-        return list(payload), "list"
-    return [payload], "array"
-
-
-def _host_weight(w):
-    if w is None:
-        return None
-    try:
-        import torch
-
-        if isinstance(w, torch.Tensor):
-            from ... import hostpipe as H
-
-            return w.detach().numpy() if w.device.type == "cpu" else H.d2h(w, pooled=False)
-    except ImportError:  # pragma: no cover
-        pass
-    return w
-
-
 def mask_payload(masker: Masker, payload, weight=None, gpu: int | None = 0):
     """Runs on the participant: quantize ``payload * weight`` and add the
     pairwise masks (``sa_mask`` on this party's GPU ``gpu``).
@@ -161,23 +128,15 @@ def mask_payload(masker: Masker, payload, weight=None, gpu: int | None = 0):
     as it was -- an object store hands the function a copy anyway, and an
     in-process device must not see a round that failed part-way advance
     some parties' streams."""
-    from .secure_aggregator import _compute_dtype, _np_dtype, _shape
-
     masker = masker.copy()
-    layers, container = _layers(payload)
-    weight = _host_weight(weight)
-    shapes = [_shape(a) for a in layers]
+    layers, container = split_layers(payload)
+    weight = host_weight(weight)
+    shapes = [shape(a) for a in layers]
     sizes = [int(np.prod(sh)) if sh else 1 for sh in shapes]
-    as_torch = _is_torch(layers[0]) if layers else False
+    as_torch = is_torch(layers[0]) if layers else False
     plan = []
     for a, sh in zip(layers, shapes):
-        ldt = _np_dtype(a)
-        ct = _compute_dtype(ldt, weight, masker.fxp_bits)
-        if ct not in (_F32, _F64, _I64):
-            raise NotImplementedError(f"arithmetic type {ct} (data {ldt}) is not supported")
-        if ldt.kind in "biu" and ldt != _I64 and ct.kind == "i":
-            raise NotImplementedError(f"integer data of type {ldt} is not supported")
-        xt = ldt if ldt in (_F32, _F64, _I64) else (_I64 if ldt.kind in "biu" else _F64)
+        xt, ct = element_types(np_dtype(a), weight, masker.fxp_bits)
         wvec = None
         if weight is not None and np.ndim(weight):
             wvec = np.ascontiguousarray(np.broadcast_to(np.asarray(weight), sh).astype(ct)).reshape(-1)
@@ -205,7 +164,7 @@ def mask_payload(masker: Masker, payload, weight=None, gpu: int | None = 0):
         xs = [layers[li] for li in lis]
         wscalar = 1.0
         if weight is not None and not np.ndim(weight):
-            wscalar = float(weight) if ct.kind == "f" else int(weight)
+            wscalar = scalar_weight(weight, ct)
         vec, extra, dig = _mask_vector(masker, xs, xt, ct, wscalar, wvec, gpu)
         if out is None and lo == 0 and hi == bounds[-1]:
             out = vec  # one group: its (fresh) vector is the payload, no copy
@@ -224,19 +183,6 @@ def mask_payload(masker: Masker, payload, weight=None, gpu: int | None = 0):
             masker)
 
 
-def _is_cuda(a) -> bool:
-    return _is_torch(a) and a.device.type != "cpu"
-
-
-def _is_torch(a) -> bool:
-    try:
-        import torch
-
-        return isinstance(a, torch.Tensor)
-    except ImportError:  # pragma: no cover
-        return False
-
-
 def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, wvec, gpu):
     """One launch group on the party's GPU: ``sa_mask`` over the packed
     layers ``xs`` from the masker's current stream positions; a flagged raw
@@ -253,13 +199,12 @@ def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, 
     from ... import _lib as L
     from ... import hostpipe as H
     from ... import kernels as K
-    from .secure_aggregator import SMALL_CALL_BYTES
 
     if gpu is None:
         raise RuntimeError("the party has no GPU: libsfl_sa masks on the device")
     dev = torch.device("cuda", gpu)
-    tdt = _torch_dtypes()
-    n = int(sum(int(np.prod(_shape_of(a))) for a in xs))
+    tdt = torch_dtypes()
+    n = int(sum(int(np.prod(shape(a))) for a in xs))
     small = 8 * n <= SMALL_CALL_BYTES
     streams = masker.streams()
     if all(not isinstance(a, torch.Tensor) or a.device.type == "cpu" for a in xs):
@@ -275,8 +220,7 @@ def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, 
         # numpy's rejection of a raw 0: the device path below re-positions the streams
     if small and wvec is None and host_layers:
         # host layers of a small payload: ONE blocking library call
-        flat = (np.asarray(xs[0], dtype=xt).reshape(-1) if len(xs) == 1 else
-                np.concatenate([np.asarray(a, dtype=xt).reshape(-1) for a in xs]))
+        flat = flat_host(xs, xt)
         with _SCRATCH_LOCK, torch.cuda.device(dev):
             pin, dbuf = _scratch(gpu, *K.mask_host_scratch(n, xt.itemsize))
             host, flag = K.mask_host(flat, ct, streams, pin, dbuf, weight=wscalar, fxp_bits=masker.fxp_bits)
@@ -296,15 +240,10 @@ def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, 
                     off += a.size
                 x = pin.to(dev, non_blocking=True)
             else:
-                flat = (np.ascontiguousarray(np.asarray(xs[0]), dtype=xt).reshape(-1) if len(xs) == 1 else
-                        np.concatenate([np.asarray(a, dtype=xt).reshape(-1) for a in xs]))
-                x = H.h2d(flat, dev)
+                x = H.h2d(flat_host(xs, xt), dev)
         else:
             # device tensors as they are; CPU tensors cast on the host (no DMA), then pinned H2D
-            parts = [a.detach().reshape(-1).to(device=dev, dtype=tdt[xt]) if _is_cuda(a) else
-                     H.h2d(a.detach().reshape(-1).to(tdt[xt]) if _is_torch(a) else
-                           np.ascontiguousarray(np.asarray(a), dtype=xt).reshape(-1), dev)
-                     for a in xs]
+            parts = [to_device(a, xt, dev) for a in xs]
             x = parts[0] if len(parts) == 1 else torch.cat(parts)
         x = x.contiguous()
         if x.data_ptr() % 16:
@@ -328,8 +267,7 @@ def _mask_vector(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype, wscalar, 
         if flag & L.SA_FLAG_PRG_REJECT:
             found = K.rejected_draws_many([g for g, _, _ in streams], n, dev)
             for peer, (gen, sign, _), (pts, total) in zip(masker.peers, streams, found):
-                for k, shift in pts:
-                    K.stream_shift(out, gen, sign, k, shift)
+                K.stream_shifts(out, gen, sign, pts)
                 if total > n:
                     extra[peer] = total - n
             host = H.d2h(out).view(np.uint64)
@@ -360,7 +298,7 @@ def _mask_vector_pipelined(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype,
     from ... import kernels as K
 
     dev = torch.device("cuda", gpu)
-    tdt = _torch_dtypes()
+    tdt = torch_dtypes()
     layers = H.host_layers(xs, xt)
     n = int(sum(a.size for a in layers))
     bounds = H.page_bounds(H.chunk_bounds(n, target=16), [layers])
@@ -385,10 +323,6 @@ def _mask_vector_pipelined(masker: Masker, xs: list, xt: np.dtype, ct: np.dtype,
     return out, {}, digest
 
 
-def _shape_of(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
 # ------------------------------------------------------------- server side
 def sum_decode(*payloads: MaskedPayload, weights=None, average: bool = False, gpu: int | None = 0):
     """Runs on the server: check each payload's digest, sum the masked
@@ -411,7 +345,7 @@ def sum_decode(*payloads: MaskedPayload, weights=None, average: bool = False, gp
         if weights is None:
             divisor = float(len(payloads))
         else:
-            weights = [_host_weight(w) for w in weights]
+            weights = [host_weight(w) for w in weights]
             assert len(weights) == len(payloads), (
                 f"Length of the weights does not match the data: {len(weights)} vs {len(payloads)}.")
             if all(np.ndim(w) == 0 for w in weights):
@@ -449,7 +383,6 @@ def _sum_decode_vectors(u64s, digests, fxp_bits, divisor, divisor_vec, gpu, as_t
 
     from ... import hostpipe as H
     from ... import kernels as K
-    from .secure_aggregator import SMALL_CALL_BYTES
 
     if gpu is None:
         raise RuntimeError("the server has no GPU: libsfl_sa sums on the device")

@@ -458,8 +458,8 @@ def test_small_call_party_counts_containers_and_weights(parties, dtype):
 @pytest.mark.parametrize("dtype", [np.int64, np.float64])
 def test_general_one_call_matches_general_path(dtype, monkeypatch):
     """small float64 / int64 host calls of 2..9 parties take ONE
-    blocking library call (``_host_general_one_call`` -> sa_clients_host).
-    The same two rounds with that path forced off (the general per-launch
+    blocking library call (route ``general_one_call`` -> sa_clients_host).
+    The same two rounds routed to ``general`` instead (the per-launch
     path) give identical results, identical per-party digests and identical
     masker positions afterwards; both equal the oracle (digests of the
     oracle's masked vectors, decoded averages)."""
@@ -485,14 +485,15 @@ def test_general_one_call_matches_general_path(dtype, monkeypatch):
     def run(one_call: bool):
         agg = SecureAggregator(PYU("server", 0), pyus, seeds=pair)
         calls = []
-        orig = agg._host_general_one_call
+        orig = agg._run_general_one_call
 
         def spy(*a, **k):
-            r = orig(*a, **k) if one_call else None
-            calls.append(r is not None)
-            return r
+            calls.append(True)
+            return orig(*a, **k)
 
-        monkeypatch.setattr(agg, "_host_general_one_call", spy)
+        monkeypatch.setattr(agg, "_run_general_one_call", spy)
+        if not one_call:
+            monkeypatch.setattr(agg, "_route", lambda call: calls.append(False) or "general")
         outs = []
         for data in rounds:
             got = rv(agg.average([p(lambda d=d: d)() for p, d in zip(pyus, data)], axis=0, weights=weights))

@@ -243,8 +243,8 @@ def test_in_process_large_general_payloads(kind, C, monkeypatch):
                   for _ in range(2)]
         weights = [int(w) for w in rng.integers(1, 5, C)]
     calls = []
-    orig = S.SecureAggregator._host_general_pipelined
-    monkeypatch.setattr(S.SecureAggregator, "_host_general_pipelined",
+    orig = S.SecureAggregator._run_general_pipelined
+    monkeypatch.setattr(S.SecureAggregator, "_run_general_pipelined",
                         lambda *a, **k: calls.append(1) or orig(*a, **k))
 
     def run(pipeline):

@@ -122,7 +122,7 @@ def test_numpy_scalar_weights_follow_numpy_1_23_value_based_casting():
     promote as before."""
     import numpy as np
 
-    from sfl_amd.security.aggregation.secure_aggregator import _compute_dtype
+    from sfl_amd.security.aggregation.payload import compute_dtype as _compute_dtype
 
     f32, f64, i64 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int64)
     cases = [(f32, np.float64(3.0), f32), (f32, np.int64(5), f32), (f32, np.float64(1e300), f64),

@@ -22,7 +22,7 @@ def main():
     from sfl_amd.security.aggregation import SecureAggregator
 
     calls = {"fast": 0, "all": 0}
-    fast, agg_fn = SecureAggregator._aggregate_host_fused, SecureAggregator._aggregate
+    fast, agg_fn = SecureAggregator._run_fused_one_call, SecureAggregator._aggregate
     prof = cProfile.Profile()
     times = []
 
@@ -39,7 +39,7 @@ def main():
         times.append(time.perf_counter() - t0)
         return r
 
-    SecureAggregator._aggregate_host_fused = fast_wrap
+    SecureAggregator._run_fused_one_call = fast_wrap
     SecureAggregator._aggregate = agg_wrap
     names = T.NAMES
     seeds = o.seeds_for(names)
