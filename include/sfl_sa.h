@@ -549,6 +549,62 @@ int sa_chacha20_blocks_host(const uint32_t key[8], uint64_t nonce, uint64_t bloc
  * reached, which no search of cipher blocks can. */
 int sa_hb_normals_f64(const uint32_t* words, uint64_t n, double sigma, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* COO transport of compressed updates and the sparse server sum: the   */
+/* reference's sparse_encode / sparse_decode (sfl/utils/compressor/     */
+/* sparse_compressor.py:234-284, wrapping sparse.COO) and the sum of    */
+/* its SparsePlainAggregator (sfl/security/aggregation/                 */
+/* sparse_plain_aggregator.py:25-139).  A tensor of n elements of       */
+/* x_type T (SA_F32 or SA_F64) is (index, data): index the flat         */
+/* positions of its non-zeros as int32, strictly ascending, data their  */
+/* values bit for bit.  Non-zero is decided on the bit pattern,         */
+/* (bits & ~sign) != 0: NaN, inf and every denormal are kept, +0.0 and  */
+/* -0.0 are dropped.  n >= 2^31 and other element types are refused.    */
+/*   encode: sa_coo_count (pass 1: every wave counts the non-zeros of   */
+/*           its contiguous index range; one block turns the counts     */
+/*           into exclusive offsets in scratch and writes the total to  */
+/*           the device word nnz_out, a uint32), then sa_coo_fill with  */
+/*           the same x, n and scratch (pass 2: an entry's rank is its  */
+/*           wave's offset plus ballot prefixes; no atomics, no sort).  */
+/*           No entry of rank >= cap is stored; a total other than cap  */
+/*           sets SA_COO_BAD_COUNT.                                     */
+/*   decode: dense_out = 0, then dense_out[index[i]] = data[i].         */
+/*   sum:    acc[index[i]] = acc[index[i]] + A(data[i]) * A(w), multiply */
+/*           and add rounded separately, for (T, A) = (f32, f32),       */
+/*           (f32, f64), (f64, f64); one launch per party on one stream */
+/*           (a valid payload's indices are unique: no float atomics,   */
+/*           the same bits on every run); then sa_coo_finish,           */
+/*           acc[i] = acc[i] / A(divisor).                              */
+/* A payload is another party's data.  decode and axpy store entry i    */
+/* only if 0 <= index[i] < n -- an index out of range is never used as  */
+/* an address -- and report into flag, two uint32 on the device that    */
+/* the caller sets to {0, 0xffffffff}: [0] the SA_COO_BAD_* bits met,   */
+/* [1] the least offending entry i (an integer atomicMin).  With a bit  */
+/* set the content of dense_out / acc is unspecified, but every store   */
+/* landed inside it.  Everything is stream-ordered and allocates        */
+/* nothing; 16-byte aligned x / acc take 16-byte loads and stores.      */
+/* ------------------------------------------------------------------ */
+#define SA_COO_BAD_RANGE 1u /* an index outside the tensor */
+#define SA_COO_BAD_ORDER 2u /* index[i] <= index[i-1]: unsorted or duplicated */
+#define SA_COO_BAD_COUNT 4u /* sa_coo_fill: the number of non-zeros is not cap */
+
+/* bytes of device scratch the encode needs for n elements (4-byte aligned;
+ * sa_coo_count writes it, sa_coo_fill reads it), or a negative SA_ERR_* code */
+int sa_coo_scratch_bytes(uint64_t n, int x_type);
+
+int sa_coo_count(const void* x, int x_type, uint64_t n, void* scratch, void* nnz_out, void* stream);
+
+int sa_coo_fill(const void* x, int x_type, uint64_t n, const void* scratch, void* index_out, void* data_out,
+                uint64_t cap, void* flag, void* stream);
+
+int sa_coo_decode(const void* index, const void* data, int x_type, uint64_t nnz, uint64_t n, void* dense_out,
+                  void* flag, void* stream);
+
+int sa_coo_axpy(const void* index, const void* data, int x_type, uint64_t nnz, double w, void* acc, int acc_type,
+                uint64_t n, void* flag, void* stream);
+
+int sa_coo_finish(void* acc, int acc_type, uint64_t n, double divisor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

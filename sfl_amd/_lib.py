@@ -24,6 +24,7 @@ SA_F32, SA_F64, SA_I64 = 0, 1, 2
 SA_FLAG_PRG_REJECT = 1
 SA_UNIQUE_ID_BYTES = 128
 SA_DP_PARTIALS = 1024
+SA_COO_BAD_RANGE, SA_COO_BAD_ORDER, SA_COO_BAD_COUNT = 1, 2, 4
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -35,6 +36,7 @@ EXPORTED = (
     "sa_comm_allreduce_u64", "sa_comm_reduce_scatter_u64", "sa_comm_alltoall_u64", "sa_comm_gather_f64", "sa_comm_info", "sa_comm_destroy", "sa_sumsq_f32", "sa_dp_perturb_f32", "sa_mask_dp",
     "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64", "sa_stc_scratch_bytes", "sa_stc",
     "sa_scr_scratch_bytes", "sa_scr",
+    "sa_coo_scratch_bytes", "sa_coo_count", "sa_coo_fill", "sa_coo_decode", "sa_coo_axpy", "sa_coo_finish",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
 )
 
@@ -134,6 +136,12 @@ def _declare(lib):
     lib.sa_stc.argtypes = [vp, vp, vp, i32, u64, u64, vp, vp, vp, vp, vp, vp]
     lib.sa_scr_scratch_bytes.argtypes = [u64, u64, u64, i32]
     lib.sa_scr.argtypes = [vp, vp, vp, i32, u64, u64, u64, dbl, vp, vp, vp, vp, vp]
+    lib.sa_coo_scratch_bytes.argtypes = [u64, i32]
+    lib.sa_coo_count.argtypes = [vp, i32, u64, vp, vp, vp]
+    lib.sa_coo_fill.argtypes = [vp, i32, u64, vp, vp, vp, u64, vp, vp]
+    lib.sa_coo_decode.argtypes = [vp, vp, i32, u64, u64, vp, vp, vp]
+    lib.sa_coo_axpy.argtypes = [vp, vp, i32, u64, dbl, vp, i32, u64, vp, vp]
+    lib.sa_coo_finish.argtypes = [vp, i32, u64, dbl, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -111,7 +111,8 @@ def _move(data, dev: PYU):
         return data.to(dev.torch_device)
     if isinstance(data, np.ndarray):
         return data.copy()
-    if type(data).__name__ == "SparseCOO" and hasattr(data, "index"):  # utils.sparse: a host form, copied like an array
+    # utils.sparse: copied like an array; a device form is cloned where it lives (index and data on its GPU)
+    if type(data).__name__ == "SparseCOO" and hasattr(data, "index"):
         return type(data)(data.shape, data.dtype, *(v.copy() if isinstance(v, np.ndarray) else v.clone()
                                                     for v in (data.index, data.data)))
     return data

@@ -576,6 +576,135 @@ def scr(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, shape3:
 
 
 # ---------------------------------------------------------------------------
+# COO transport and the sparse server sum (sa_coo_*; utils/sparse.py and
+# SparsePlainAggregator on top)
+# ---------------------------------------------------------------------------
+_COO_FLOATS = (torch.float32, torch.float64)
+
+
+def _coo_float(what: str, dtype) -> int:
+    if dtype not in _COO_FLOATS:
+        raise TypeError(f"{what}: float32 or float64, not {dtype}")
+    return xtype_of(dtype)
+
+
+def _coo_words(what: str, name: str, t: torch.Tensor, words: int) -> None:
+    if t.dtype != torch.int32 or t.numel() < words or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} is {words} contiguous int32 word{'s' if words > 1 else ''}")
+
+
+def _coo_payload(what: str, index: torch.Tensor, data: torch.Tensor) -> int:
+    xt = _coo_float(what, data.dtype)
+    if index.dtype != torch.int32 or index.dim() != 1 or data.dim() != 1 or index.numel() != data.numel() \
+            or not index.is_contiguous() or not data.is_contiguous():
+        raise ValueError(f"{what}: index (int32) and data are flat contiguous tensors of one length")
+    return xt
+
+
+def coo_scratch_bytes(n: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``coo_count`` / ``coo_fill`` need for ``n`` elements of ``dtype``."""
+    xt = _coo_float("coo_scratch_bytes", dtype)
+    rc = L.lib().sa_coo_scratch_bytes(int(n), xt)
+    if rc < 0:
+        L.check(rc, "sa_coo_scratch_bytes")
+    return rc
+
+
+def coo_flag(device) -> torch.Tensor:
+    """A fresh flag record for ``coo_fill`` / ``coo_decode`` / ``coo_axpy``:
+    no bit set, no offending position (``[0, -1]`` as int32)."""
+    flag = torch.zeros(2, dtype=torch.int32, device=device)
+    flag[1] = -1
+    return flag
+
+
+def coo_count(x: torch.Tensor, scratch: torch.Tensor, nnz_out: torch.Tensor) -> torch.Tensor:
+    """The encode's first pass: the number of non-zeros of ``x`` (by the bit
+    rule) into the device word ``nnz_out`` (one int32), and every wave's
+    first rank into ``scratch`` for ``coo_fill``.  See sa_coo_count in
+    include/sfl_sa.h."""
+    _require_gpu(x, scratch, nnz_out)
+    xt = _coo_float("coo_count", x.dtype)
+    if not x.is_contiguous():
+        raise ValueError("coo_count: a contiguous tensor")
+    _coo_words("coo_count", "nnz_out", nnz_out, 1)
+    if scratch.numel() * scratch.element_size() < coo_scratch_bytes(x.numel(), x.dtype):
+        raise ValueError("coo_count: scratch smaller than coo_scratch_bytes(n, dtype)")
+    L.check(L.lib().sa_coo_count(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(nnz_out), C.c_void_p(_stream(x))),
+            "sa_coo_count")
+    return nnz_out
+
+
+def coo_fill(x: torch.Tensor, scratch: torch.Tensor, index_out: torch.Tensor, data_out: torch.Tensor,
+             flag: torch.Tensor, *, cap: int | None = None) -> None:
+    """The encode's second pass, after ``coo_count`` of the same ``x`` into
+    the same ``scratch``: the flat indices (int32, ascending) and the values
+    of the non-zeros.  At most ``cap`` entries (default: the outputs' length)
+    are stored; a count other than ``cap`` sets ``SA_COO_BAD_COUNT`` in
+    ``flag``."""
+    _require_gpu(x, scratch, index_out, data_out, flag)
+    xt = _coo_float("coo_fill", x.dtype)
+    if not x.is_contiguous():
+        raise ValueError("coo_fill: a contiguous tensor")
+    if data_out.dtype != x.dtype:
+        raise ValueError("coo_fill: data_out has the tensor's dtype")
+    _coo_payload("coo_fill", index_out, data_out)
+    _coo_words("coo_fill", "flag", flag, 2)
+    cap = index_out.numel() if cap is None else int(cap)
+    if not 0 <= cap <= min(index_out.numel(), x.numel()):
+        raise ValueError("coo_fill: cap outside [0, min(len(index_out), n)]")
+    if scratch.numel() * scratch.element_size() < coo_scratch_bytes(x.numel(), x.dtype):
+        raise ValueError("coo_fill: scratch smaller than coo_scratch_bytes(n, dtype)")
+    L.check(L.lib().sa_coo_fill(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(index_out), _ptr(data_out), cap,
+                                _ptr(flag), C.c_void_p(_stream(x))), "sa_coo_fill")
+
+
+def coo_decode(index: torch.Tensor, data: torch.Tensor, dense_out: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """dense_out = 0, then dense_out[index[i]] = data[i] for every entry
+    inside the tensor; what was wrong with the payload goes into ``flag``."""
+    _require_gpu(index, data, dense_out, flag)
+    xt = _coo_payload("coo_decode", index, data)
+    if dense_out.dtype != data.dtype or not dense_out.is_contiguous():
+        raise ValueError("coo_decode: dense_out is contiguous and has the data's dtype")
+    if index.numel() > dense_out.numel():
+        raise ValueError("coo_decode: more entries than the tensor has elements")
+    _coo_words("coo_decode", "flag", flag, 2)
+    L.check(L.lib().sa_coo_decode(_ptr(index), _ptr(data), xt, index.numel(), dense_out.numel(), _ptr(dense_out),
+                                  _ptr(flag), C.c_void_p(_stream(dense_out))), "sa_coo_decode")
+    return dense_out
+
+
+def coo_axpy(index: torch.Tensor, data: torch.Tensor, w: float, acc: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """acc[index[i]] = acc[index[i]] + A(data[i]) * A(w), multiply and add
+    rounded separately, ``A`` the accumulator's type (float32 data: float32 or
+    float64; float64 data: float64).  Validates like ``coo_decode``."""
+    _require_gpu(index, data, acc, flag)
+    xt = _coo_payload("coo_axpy", index, data)
+    at = _coo_float("coo_axpy", acc.dtype)
+    if data.dtype == torch.float64 and acc.dtype == torch.float32:
+        raise TypeError("coo_axpy: float64 data needs a float64 accumulator")
+    if not acc.is_contiguous():
+        raise ValueError("coo_axpy: a contiguous accumulator")
+    if index.numel() > acc.numel():
+        raise ValueError("coo_axpy: more entries than the tensor has elements")
+    _coo_words("coo_axpy", "flag", flag, 2)
+    L.check(L.lib().sa_coo_axpy(_ptr(index), _ptr(data), xt, index.numel(), float(w), _ptr(acc), at, acc.numel(),
+                                _ptr(flag), C.c_void_p(_stream(acc))), "sa_coo_axpy")
+    return acc
+
+
+def coo_finish(acc: torch.Tensor, divisor: float) -> torch.Tensor:
+    """acc[i] = acc[i] / A(divisor) in place."""
+    _require_gpu(acc)
+    at = _coo_float("coo_finish", acc.dtype)
+    if not acc.is_contiguous():
+        raise ValueError("coo_finish: a contiguous accumulator")
+    L.check(L.lib().sa_coo_finish(_ptr(acc), at, acc.numel(), float(divisor), C.c_void_p(_stream(acc))),
+            "sa_coo_finish")
+    return acc
+
+
+# ---------------------------------------------------------------------------
 # numpy's rejection re-draw (after SA_FLAG_PRG_REJECT; never on the hot path)
 # ---------------------------------------------------------------------------
 U64_MAX = (1 << 64) - 1

@@ -39,7 +39,9 @@ work runs in the HIP kernels of ``sfl_amd.utils.compressor`` wherever
 ``compress_device`` is a GPU.  By default the ternary tensors travel dense:
 the secure aggregator masks every element and has no sparse input.
 ``sparse_transport`` ("down" or "both") puts them into COO form
-(``sfl_amd.utils.sparse``, built on the host) as the reference's ``sparse_encode`` does at the
+(``sfl_amd.utils.sparse``: on the host for host payloads, by the ``sa_coo``
+kernels for a GPU model's, which then never take the dense form on the host)
+as the reference's ``sparse_encode`` does at the
 end of ``train_step`` (``fed_stc.py:128``, ``fed_scr.py:126``) and on the
 server's downstream (``fl_model.py:558-563``); sparse uploads ("both") need
 an aggregator that takes them, ``SparsePlainAggregator``.  ``fed_scr`` (structure-wise pruning of
@@ -526,11 +528,6 @@ class FLModel:
         self._workers: Dict[PYU, FedAvgW] = {
             d: _STRATEGIES[(strategy, backend)](model, d, random_seed, train_device, **kwargs)
             for d in self.device_list}
-        if sparse_transport is not None and any(w._resident for w in self._workers.values()):
-            raise ValueError("sparse_transport: the COO form is built on the host (it has no device kernel yet), and "
-                             "a GPU model compressed on its own GPU keeps its payload on the device; train with "
-                             "train_device='cpu' (compress_device may be the GPU: the payload then comes back "
-                             "through pinned memory)")
 
     def initialize_weights(self):
         """Average the clients' initial weights through the aggregator and
@@ -550,10 +547,11 @@ class FLModel:
         own copy of the model.  Gives (the sparse update, what goes back to
         the parties: the same, or its COO form with ``sparse_transport``,
         fl_model.py:558-563)."""
-        if isinstance(agg_data[0], torch.Tensor) and agg_data[0].is_cuda and \
-                not isinstance(self.server_weight[0], torch.Tensor):
-            # device payloads: the server's copy follows the aggregate onto its device
-            self.server_weight = [H.h2d(w, a.device) for w, a in zip(self.server_weight, agg_data)]
+        # device payloads: the server's copy follows the aggregate onto its device, layer by
+        # layer (a sparse aggregator's device sums stay there, its numpy fall-backs are arrays)
+        self.server_weight = [H.h2d(w, a.device) if isinstance(a, torch.Tensor) and a.is_cuda
+                              and not isinstance(w, torch.Tensor) else w
+                              for w, a in zip(self.server_weight, agg_data)]
         # a plain aggregator's unweighted initial average keeps the model's float32 while
         # its weighted averages are float64 (numpy's promotion): the server's copy follows
         # the aggregate's type too (a no-op with an aggregator whose results are all float64)
@@ -607,7 +605,7 @@ class FLModel:
                 t_agg = time.perf_counter()
                 model_params = self._aggregator.average(params, axis=0, weights=nums)
                 agg_data = reveal(model_params)
-                if isinstance(agg_data, list) and agg_data and isinstance(agg_data[0], torch.Tensor):
+                if isinstance(agg_data, list) and any(isinstance(a, torch.Tensor) and a.is_cuda for a in agg_data):
                     torch.cuda.synchronize()
                 history["aggregation_s"].append(time.perf_counter() - t_agg)
                 if self.strategy == "fed_stc":

@@ -5,9 +5,12 @@ Over ``axis=0`` (the parties) a list of ``SparseCOO`` entries is never
 decoded: a dense accumulator is zeroed, every party's non-zeros are added
 into it in list order (``acc[i] = acc[i] + A(x) * A(w)``, multiply and add
 rounded separately) and, for an average, divided once.  The server's work is
-proportional to the non-zeros it receives, not to parties x elements.  It
-runs in numpy on the host: the COO form has no device kernel yet, and results
-are numpy arrays.
+proportional to the non-zeros it receives, not to parties x elements.  Host
+entries run numpy and give numpy arrays.  When entries of a layer are device
+``SparseCOO``s the accumulator is a tensor on their device: one
+``kernels.coo_axpy`` per party in list order, ``kernels.coo_finish`` for an
+average, one read of the parties' flag records after the last party; the
+result stays on the device and has the host path's bits.
 
 Accumulator type ``A`` and divisor follow numpy, and the result equals
 numpy's over the decoded arrays bit for bit (the sign of a zero apart: the
@@ -44,7 +47,7 @@ _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 def _to_host(x, name: str):
     c = S.as_coo(x, name)
     if c is not None:
-        x = S._decode_one(c, name)
+        x = S._decode_one(c.to("cpu") if c.is_device else c, name)  # device entries: through pinned memory
     if isinstance(x, torch.Tensor):
         from ... import hostpipe as H
 
@@ -96,6 +99,9 @@ class SparsePlainAggregator(Aggregator):
             scl = T.type(K)
         for k, c in enumerate(entries):
             S._check_form(c, f"{name}, party {k}")
+        dev = next((c.data.device for c in entries if c.is_device), None)
+        if dev is not None and np.dtype(A) in _FLOATS:  # any other A (complex weights): numpy below
+            return self._device_axis0(entries, ws, A, scl if average else None, dev, name).reshape(shape)
         acc = np.zeros(n, dtype=A)
         for k, (c, w) in enumerate(zip(entries, ws)):
             index, data = S._host(c.index), S._host(c.data)
@@ -106,6 +112,30 @@ class SparsePlainAggregator(Aggregator):
             with np.errstate(invalid="ignore", divide="ignore"):
                 acc = acc / scl
         return acc.reshape(shape)
+
+    @staticmethod
+    def _device_axis0(entries: List[S.SparseCOO], ws: List[float], A, scl, dev, name: str) -> torch.Tensor:
+        """The same sum on ``dev``: the accumulator is zeroed once, every
+        party is one launch on one stream (a valid payload's indices are
+        unique, so no two threads meet in an element), and the flag records
+        of all parties are read once at the end."""
+        from ... import kernels as K
+
+        n = entries[0].size
+        acc = torch.zeros(n, dtype=getattr(torch, np.dtype(A).name), device=dev)
+        flags = torch.zeros((len(entries), 2), dtype=torch.int32, device=dev)
+        flags[:, 1] = -1
+        for k, (c, w) in enumerate(zip(entries, ws)):
+            if not c.is_device or c.data.device != dev:
+                c = c.to(dev)  # host entries among them: through pinned memory
+            K.coo_axpy(c.index.contiguous(), c.data.contiguous(), w, acc, flags[k])
+        if scl is not None:
+            K.coo_finish(acc, float(scl))
+        for k, (bits, _) in enumerate(S._read_words(flags)):
+            err = S.flag_error(int(bits), n, f"{name}, party {k}")
+            if err is not None:
+                raise err
+        return acc
 
     def _entry(self, xs: list, axis, weights, average: bool, name: str):
         """One layer's (or one single entry's) values of every party."""

@@ -8,15 +8,17 @@ C-order positions of its non-zeros, ``int32``, strictly ascending) and
 pattern**, ``(bits & ~sign) != 0``: NaN, inf and every denormal are kept,
 ``+0.0`` and ``-0.0`` are dropped, and a dropped ``-0.0`` decodes as ``+0.0``.
 
-This is the host form: numpy arrays and CPU tensors, of any element type
-(integer entries of a state dict, ``num_batches_tracked``, included), run
-numpy.  There is no device kernel for it yet, and a CUDA tensor is refused
-with ``NotImplementedError`` rather than carried across the host quietly: a
-GPU worker that wants sparse transport compresses on its GPU and uploads from
-the host (``FedSTC`` with a host model and a GPU ``compress_device``).  A
-payload is another party's data: decoding validates every entry (inside the
-tensor, strictly ascending, hence unique) and raises ``ValueError`` naming
-the tensor.
+There are two forms.  The host form: numpy arrays and CPU tensors, of any
+element type (integer entries of a state dict, ``num_batches_tracked``,
+included), run numpy.  The device form: a CUDA float32 / float64 tensor is
+encoded and decoded where it lives by the ``sa_coo_*`` kernels
+(``sfl_amd/csrc/sa_coo.hip``: count, one pinned read of ``nnz``, fill; a
+validated scatter), and ``index`` and ``data`` are tensors on that device.  A
+CUDA tensor of any other element type is a counter of a few elements: it comes
+to the host through pinned memory and takes the host form.  A payload is
+another party's data: decoding validates every entry (inside the tensor,
+strictly ascending, hence unique) and raises ``ValueError`` naming the tensor,
+with the same words in both forms.
 """
 
 from __future__ import annotations
@@ -54,8 +56,8 @@ def nonzero_mask(flat: np.ndarray) -> np.ndarray:
 
 class SparseCOO:
     """One tensor in COO form.  ``index`` and ``data`` are two numpy arrays,
-    or two CPU tensors; ``dtype`` is the dense tensor's element
-    type as a numpy dtype."""
+    or two tensors on one device (the CPU or a GPU); ``dtype`` is the dense
+    tensor's element type as a numpy dtype."""
 
     __slots__ = ("shape", "dtype", "index", "data")
 
@@ -90,28 +92,45 @@ class SparseCOO:
         return _decode_one(self, "SparseCOO")
 
     def to(self, device) -> "SparseCOO":
-        """Index and data on ``device`` (a torch device).  Only the CPU holds a
-        ``SparseCOO`` in this build: there they are numpy arrays."""
-        if torch.device(device).type != "cpu":
-            raise _no_kernel("SparseCOO.to")
-        return SparseCOO(self.shape, self.dtype, _host(self.index), _host(self.data))
+        """Index and data on ``device`` (a torch device): numpy arrays on the
+        CPU, tensors on a GPU.  Host and device exchange them through pinned
+        memory (``hostpipe.h2d`` / ``d2h``)."""
+        device = torch.device(device)
+        if device.type == "cpu":
+            return SparseCOO(self.shape, self.dtype, _host(self.index), _host(self.data))
+        from .. import hostpipe as H
+
+        return SparseCOO(self.shape, self.dtype, H.h2d(self.index, device), H.h2d(self.data, device))
+
+    @property
+    def is_device(self) -> bool:
+        return isinstance(self.data, torch.Tensor) and self.data.is_cuda
 
     def __repr__(self):
         where = str(self.data.device) if isinstance(self.data, torch.Tensor) else "host"
         return f"SparseCOO(shape={self.shape}, dtype={self.dtype}, nnz={self.nnz}, {where})"
 
 
-def _no_kernel(what: str) -> NotImplementedError:
-    return NotImplementedError(f"{what}: there is no device kernel for the COO form in this build; "
-                               f"encode and decode host arrays (CPU tensors, numpy)")
-
-
 def _host(a) -> np.ndarray:
     if isinstance(a, torch.Tensor):
         if a.is_cuda:
-            raise _no_kernel("SparseCOO")
+            from .. import hostpipe as H
+
+            if a.numel() == 0:
+                return np.empty(tuple(a.shape), dtype=H.host_dtype(a))
+            return H.d2h(a, pooled=False)  # pinned, never a pageable DMA
         return a.detach().numpy()
     return np.asarray(a)
+
+
+_DEVICE_FLOATS = (torch.float32, torch.float64)
+
+
+def _read_words(t: torch.Tensor) -> np.ndarray:
+    """A few device words on the host through a pinned buffer (blocking)."""
+    from .. import hostpipe as H
+
+    return H.d2h(t, pooled=False)
 
 
 # ---------------------------------------------------------------------------
@@ -125,12 +144,37 @@ def _encode_host(x: np.ndarray) -> SparseCOO:
     return SparseCOO(x.shape, x.dtype, idx.astype(np.int32), flat[idx])
 
 
+def _encode_device(x: torch.Tensor) -> SparseCOO:
+    """count, one pinned read of nnz, allocation, fill: index and data on x's device."""
+    from .. import kernels as K
+
+    flat = x.detach().contiguous().reshape(-1)
+    n, dev = flat.numel(), flat.device
+    if n >= _MAX_N:
+        raise ValueError("sparse_encode: a tensor of 2^31 elements or more has no int32 flat index")
+    nnz = 0
+    if n:
+        scratch = torch.empty(K.coo_scratch_bytes(n, flat.dtype) // 4, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        K.coo_count(flat, scratch, count)
+        nnz = int(_read_words(count)[0])
+    index = torch.empty(nnz, dtype=torch.int32, device=dev)
+    data = torch.empty(nnz, dtype=flat.dtype, device=dev)
+    if nnz:
+        # x has not changed since the count (one stream), so the count holds and the flag is
+        # not read; were it to differ, no entry beyond nnz would be stored
+        K.coo_fill(flat, scratch, index, data, K.coo_flag(dev))
+    return SparseCOO(x.shape, x.dtype, index, data)
+
+
 def _encode_one(x):
     if isinstance(x, SparseCOO):
         return x
     if isinstance(x, torch.Tensor):
         if x.is_cuda:
-            raise _no_kernel("sparse_encode")
+            if x.dtype in _DEVICE_FLOATS:
+                return _encode_device(x)
+            return _encode_host(_host(x))  # a counter of a few elements: the host form
         c = _encode_host(x.detach().numpy())  # a CPU tensor stays one: two CPU tensors
         return SparseCOO(c.shape, c.dtype, torch.from_numpy(c.index), torch.from_numpy(c.data))
     return _encode_host(np.asarray(x))
@@ -138,7 +182,12 @@ def _encode_one(x):
 
 def sparse_encode(data: List, encode_method: str = "coo") -> List:
     """The reference's ``sparse_encode``: every entry of ``data`` as a
-    ``SparseCOO`` (``None`` gives ``None``)."""
+    ``SparseCOO`` (``None`` gives ``None``).  A host array gives the host form
+    and a CPU tensor two CPU tensors.  A CUDA float32 / float64 tensor is
+    encoded on its device and gives index and data on that device.  A CUDA
+    tensor of any other element type (a state dict's ``num_batches_tracked``)
+    is a counter of a few elements: it comes to the host through pinned memory
+    (``hostpipe.d2h``) and gives a host ``SparseCOO`` of numpy arrays."""
     if data is None:
         return None
     assert encode_method in ["coo", "gcxs"], f"Get unsupport sparse encoding method: {encode_method}, "
@@ -187,8 +236,40 @@ def _check_form(c: SparseCOO, name: str):
         raise _invalid(name, "more entries than the tensor has elements")
 
 
+def flag_error(bits: int, n: int, name: str) -> Optional[ValueError]:
+    """What a device flag record (``SA_COO_BAD_*``) says, in
+    ``check_host_payload``'s words and order; None when nothing is set."""
+    from .._lib import SA_COO_BAD_ORDER, SA_COO_BAD_RANGE
+
+    if bits & SA_COO_BAD_RANGE:
+        return _invalid(name, f"an index lies outside the tensor's {n} elements")
+    if bits & SA_COO_BAD_ORDER:
+        return _invalid(name, "the indices are not strictly ascending (unsorted or duplicated)")
+    return None
+
+
+def _decode_device(c: SparseCOO, name: str) -> torch.Tensor:
+    from .. import kernels as K
+
+    dev = c.data.device
+    if c.data.dtype not in _DEVICE_FLOATS:  # not what sparse_encode makes: decoded on the host
+        from .. import hostpipe as H
+
+        return H.h2d(_decode_one(c.to("cpu"), name), dev)
+    dense = torch.empty(c.size, dtype=c.data.dtype, device=dev)
+    if c.size:
+        flag = K.coo_flag(dev)
+        K.coo_decode(c.index.contiguous(), c.data.contiguous(), dense, flag)
+        err = flag_error(int(_read_words(flag)[0]), c.size, name)
+        if err is not None:
+            raise err
+    return dense.reshape(c.shape)
+
+
 def _decode_one(c: SparseCOO, name: str):
     _check_form(c, name)
+    if c.is_device:
+        return _decode_device(c, name)
     index, data = _host(c.index), _host(c.data)
     check_host_payload(index, c.size, name)
     dense = np.zeros(c.size, dtype=c.dtype)
@@ -225,8 +306,9 @@ def as_coo(x, name: str = "entry") -> Optional[SparseCOO]:
 def sparse_decode(data: List) -> List:
     """The reference's ``sparse_decode``: the dense tensors of a list of
     ``SparseCOO``s (or of objects with ``coords``, ``data`` and ``shape``).
-    numpy payloads give numpy arrays, CPU-tensor payloads CPU tensors.  An
-    invalid payload raises ``ValueError``."""
+    numpy payloads give numpy arrays, CPU-tensor payloads CPU tensors, device
+    payloads tensors on their device.  An invalid payload raises
+    ``ValueError``."""
     if data is None:
         return None
     out = []
