@@ -605,6 +605,93 @@ int sa_coo_axpy(const void* index, const void* data, int x_type, uint64_t nnz, d
 
 int sa_coo_finish(void* acc, int acc_type, uint64_t n, double divisor, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* Quantized compressors: the reference's QuantizedZeroPoint,           */
+/* QuantizedLSTM and QuantizedFP at 8 bits (sfl/utils/compressor/       */
+/* quantized_compressor.py:65-228).  A tensor of n elements of x_type T */
+/* (SA_F32 or SA_F64) becomes n codes of q_bytes bytes (1: int8,        */
+/* 2: int16) and a few host scalars.  Every operation is rounded in T,  */
+/* never fused; `/` is IEEE division, never a multiply by a reciprocal; */
+/* rint is round-half-to-even (np.round).  This is the reference's code */
+/* as numpy 2 evaluates it (NEP 50: a Python scalar never widens T).    */
+/*                                                                      */
+/* The scalars are computed on the host between two launches:           */
+/*   sa_quant_range   out3 = (min, max, max|x|) of x as three T on the  */
+/*           device.  NaN propagates as in np.min / np.max: one NaN     */
+/*           anywhere makes all three NaN.  n = 0 gives (inf, -inf, 0). */
+/*           The sign of a zero result is unspecified.  Two stages:     */
+/*           every block reduces its share to one partial in scratch,   */
+/*           one block reduces the partials; no atomics, so the same    */
+/*           input gives the same bits on every run.                    */
+/*   zero point (mode SA_QUANT_ZERO_POINT; p0 = scale, p1 = z), for     */
+/*           qmin = -2^(bits-1), qmax = 2^(bits-1) - 1:                 */
+/*             scale = T(max - min) / T(qmax - qmin)                    */
+/*             z     = qmin - T(min / scale), clamped to [qmin, qmax],  */
+/*                     truncated to an integer                          */
+/*             code  = int(rint(min(max(x / scale + T(z), qmin), qmax))) */
+/*             dec   = (T(code) - T(z)) * scale                         */
+/*   LSTM (mode SA_QUANT_LSTM; p0 = q, p1 = T(rqm)):                    */
+/*             q     = T(2^bits - 1) / T(max - min)                     */
+/*             rqm   = int(rint(T(q * min))) + 2^(bits-1)               */
+/*             code  = int(min(max(rint(q * x) - T(rqm), qmin), qmax))  */
+/*             dec   = (T(code) + T(rqm)) / q                           */
+/*           with [qmin, qmax] the storage range of the codes.  The     */
+/*           clamp is a refinement: the reference casts without it, and */
+/*           an out-of-range float-to-int8 cast wraps on x86, turning   */
+/*           the largest element into the smallest.                     */
+/*   fp8 (mant_len, exp_offset) = (8, 6) for E4M3 with max_value 448,   */
+/*           (4, 14) for E5M2 with max_value 57344:                     */
+/*             scale = T(max_value) / (max|x| > 0 ? max|x| : 1)         */
+/*             m, e  = frexp(|x| * scale)                               */
+/*             qe    = e > -exp_offset ? e + exp_offset : 0             */
+/*             qm    = rint((2 m - 1) * mant_len); qm = mant_len is a   */
+/*                     carry into the exponent field, as intended       */
+/*             code  = sign(x) * (qe * mant_len + qm)       (an int8)   */
+/*             c     = |code| as an int32, so -128 is 128 (numpy's int8 */
+/*                     abs wraps: the second refinement; the encoder    */
+/*                     never emits -128)                                */
+/*             dec   = sign(code) * ldexp(((c % mant_len) / T(mant_len) */
+/*                     + 1) / 2, c / mant_len - exp_offset) / scale     */
+/*           A scaled magnitude below 2^-exp_offset gets qe = 0 and     */
+/*           keeps its mantissa field only, as in the reference: it     */
+/*           decodes into [2^-(exp_offset+1), 2^-exp_offset) / scale,   */
+/*           or to 0 when that field is 0; x = 0 gives code 0.          */
+/* p0, p1 and scale are doubles that carry T values exactly.  The       */
+/* kernels do not validate the scalars: the callers refuse a range that */
+/* is not finite (sfl_amd/utils/quantized.py), and x outside what the   */
+/* scalars were computed for gives saturated or unspecified codes, but  */
+/* every store lands inside q_out / out.                                */
+/* A lane packs the codes of consecutive elements in registers and      */
+/* stores at least 4 bytes at once; a scalar head of fewer than 16      */
+/* elements aligns the codes for that store, a scalar tail takes what   */
+/* is left of the last run.  The float vector takes 16-byte accesses if */
+/* it is 16-byte aligned behind the head.  Every vector is element-     */
+/* aligned; nothing may alias.  n >= 2^32, other element types, q_bytes */
+/* other than 1 or 2, an unknown mode or fp8 format and a clamp range   */
+/* outside the storage type are refused before any launch.  Everything  */
+/* is stream-ordered and allocates nothing.                             */
+/* ------------------------------------------------------------------ */
+#define SA_QUANT_ZERO_POINT 0
+#define SA_QUANT_LSTM 1
+
+/* bytes of device scratch sa_quant_range needs for n elements (8-byte
+ * aligned, rewritten by every call), or a negative SA_ERR_* code */
+int sa_quant_scratch_bytes(uint64_t n, int x_type);
+
+int sa_quant_range(const void* x, int x_type, uint64_t n, void* scratch, void* out3, void* stream);
+
+int sa_quant_affine(const void* x, int x_type, uint64_t n, int mode, double p0, double p1, int qmin, int qmax,
+                    void* q_out, int q_bytes, void* stream);
+
+int sa_dequant_affine(const void* q, int q_bytes, uint64_t n, int mode, double p0, double p1, int x_type, void* out,
+                      void* stream);
+
+int sa_quant_fp8(const void* x, int x_type, uint64_t n, double scale, int mant_len, int exp_offset, void* q_out,
+                 void* stream);
+
+int sa_dequant_fp8(const void* q, uint64_t n, double scale, int mant_len, int exp_offset, int x_type, void* out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ SA_FLAG_PRG_REJECT = 1
 SA_UNIQUE_ID_BYTES = 128
 SA_DP_PARTIALS = 1024
 SA_COO_BAD_RANGE, SA_COO_BAD_ORDER, SA_COO_BAD_COUNT = 1, 2, 4
+SA_QUANT_ZERO_POINT, SA_QUANT_LSTM = 0, 1
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -37,6 +38,8 @@ EXPORTED = (
     "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64", "sa_stc_scratch_bytes", "sa_stc",
     "sa_scr_scratch_bytes", "sa_scr",
     "sa_coo_scratch_bytes", "sa_coo_count", "sa_coo_fill", "sa_coo_decode", "sa_coo_axpy", "sa_coo_finish",
+    "sa_quant_scratch_bytes", "sa_quant_range", "sa_quant_affine", "sa_dequant_affine", "sa_quant_fp8",
+    "sa_dequant_fp8",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
 )
 
@@ -142,6 +145,12 @@ def _declare(lib):
     lib.sa_coo_decode.argtypes = [vp, vp, i32, u64, u64, vp, vp, vp]
     lib.sa_coo_axpy.argtypes = [vp, vp, i32, u64, dbl, vp, i32, u64, vp, vp]
     lib.sa_coo_finish.argtypes = [vp, i32, u64, dbl, vp]
+    lib.sa_quant_scratch_bytes.argtypes = [u64, i32]
+    lib.sa_quant_range.argtypes = [vp, i32, u64, vp, vp, vp]
+    lib.sa_quant_affine.argtypes = [vp, i32, u64, i32, dbl, dbl, i32, i32, vp, i32, vp]
+    lib.sa_dequant_affine.argtypes = [vp, i32, u64, i32, dbl, dbl, i32, vp, vp]
+    lib.sa_quant_fp8.argtypes = [vp, i32, u64, dbl, i32, i32, vp, vp]
+    lib.sa_dequant_fp8.argtypes = [vp, u64, dbl, i32, i32, i32, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

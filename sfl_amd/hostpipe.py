@@ -94,7 +94,8 @@ def chunk_bounds(n: int, target: int | None = None, lo_elems: int = 1 << 20, hi_
 
 
 _NP_OF = {"torch.float32": np.float32, "torch.float64": np.float64, "torch.float16": np.float16,
-          "torch.int64": np.int64, "torch.int32": np.int32, "torch.uint8": np.uint8, "torch.bool": np.bool_}
+          "torch.int64": np.int64, "torch.int32": np.int32, "torch.int16": np.int16, "torch.int8": np.int8,
+          "torch.uint8": np.uint8, "torch.bool": np.bool_}
 
 
 def host_dtype(t):

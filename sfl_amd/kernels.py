@@ -705,6 +705,86 @@ def coo_finish(acc: torch.Tensor, divisor: float) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# quantized compressors (sa_quant_*; utils/quantized.py on top)
+# ---------------------------------------------------------------------------
+_QUANT_CODES = {torch.int8: 1, torch.int16: 2}
+
+
+def _quant_pair(what: str, x: torch.Tensor, q: torch.Tensor, codes=_QUANT_CODES) -> tuple[int, int]:
+    """(x_type, q_bytes) of a float tensor and its codes: contiguous, one length, one device."""
+    _require_gpu(x, q)
+    xt = _coo_float(what, x.dtype)
+    if q.dtype not in codes:
+        raise TypeError(f"{what}: the codes are {' or '.join(str(d) for d in codes)}, not {q.dtype}")
+    if not x.is_contiguous() or not q.is_contiguous() or x.numel() != q.numel() or x.device != q.device:
+        raise ValueError(f"{what}: the data and the codes are contiguous tensors of one length on one device")
+    return xt, codes[q.dtype]
+
+
+def quant_scratch_bytes(n: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``quant_range`` needs for ``n`` elements of ``dtype``."""
+    xt = _coo_float("quant_scratch_bytes", dtype)
+    rc = L.lib().sa_quant_scratch_bytes(int(n), xt)
+    if rc < 0:
+        L.check(rc, "sa_quant_scratch_bytes")
+    return rc
+
+
+def quant_range(x: torch.Tensor, scratch: torch.Tensor, out3: torch.Tensor) -> torch.Tensor:
+    """``out3 = (min, max, max|x|)`` of ``x``, three elements of its dtype on
+    the device, NaN-propagating.  See sa_quant_range in include/sfl_sa.h."""
+    _require_gpu(x, scratch, out3)
+    xt = _coo_float("quant_range", x.dtype)
+    if not x.is_contiguous():
+        raise ValueError("quant_range: a contiguous tensor")
+    if out3.dtype != x.dtype or out3.numel() < 3 or not out3.is_contiguous():
+        raise ValueError("quant_range: out3 is three contiguous elements of the data's dtype")
+    if scratch.numel() * scratch.element_size() < quant_scratch_bytes(x.numel(), x.dtype):
+        raise ValueError("quant_range: scratch smaller than quant_scratch_bytes(n, dtype)")
+    L.check(L.lib().sa_quant_range(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(out3), C.c_void_p(_stream(x))),
+            "sa_quant_range")
+    return out3
+
+
+def quant_affine(x: torch.Tensor, mode: int, p0: float, p1: float, qmin: int, qmax: int,
+                 q_out: torch.Tensor) -> torch.Tensor:
+    """The codes of ``x`` into ``q_out`` (int8 or int16).  ``mode``
+    ``L.SA_QUANT_ZERO_POINT``: ``p0 = scale``, ``p1 = z``; ``L.SA_QUANT_LSTM``:
+    ``p0 = q``, ``p1 = rqm`` rounded to the data's type.  See sa_quant_affine."""
+    xt, qb = _quant_pair("quant_affine", x, q_out)
+    L.check(L.lib().sa_quant_affine(_ptr(x), xt, x.numel(), int(mode), float(p0), float(p1), int(qmin), int(qmax),
+                                    _ptr(q_out), qb, C.c_void_p(_stream(x))), "sa_quant_affine")
+    return q_out
+
+
+def dequant_affine(q: torch.Tensor, mode: int, p0: float, p1: float, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float32 / float64) from the codes ``q``; the parameters as in ``quant_affine``."""
+    xt, qb = _quant_pair("dequant_affine", out, q)
+    L.check(L.lib().sa_dequant_affine(_ptr(q), qb, q.numel(), int(mode), float(p0), float(p1), xt, _ptr(out),
+                                      C.c_void_p(_stream(out))), "sa_dequant_affine")
+    return out
+
+
+_FP8_CODES = {torch.int8: 1}
+
+
+def quant_fp8(x: torch.Tensor, scale: float, mant_len: int, exp_offset: int, q_out: torch.Tensor) -> torch.Tensor:
+    """The fp8 codes of ``x`` into ``q_out`` (int8).  See sa_quant_fp8."""
+    xt, _ = _quant_pair("quant_fp8", x, q_out, _FP8_CODES)
+    L.check(L.lib().sa_quant_fp8(_ptr(x), xt, x.numel(), float(scale), int(mant_len), int(exp_offset), _ptr(q_out),
+                                 C.c_void_p(_stream(x))), "sa_quant_fp8")
+    return q_out
+
+
+def dequant_fp8(q: torch.Tensor, scale: float, mant_len: int, exp_offset: int, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float32 / float64) from the fp8 codes ``q`` (int8)."""
+    xt, _ = _quant_pair("dequant_fp8", out, q, _FP8_CODES)
+    L.check(L.lib().sa_dequant_fp8(_ptr(q), q.numel(), float(scale), int(mant_len), int(exp_offset), xt, _ptr(out),
+                                   C.c_void_p(_stream(out))), "sa_dequant_fp8")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # numpy's rejection re-draw (after SA_FLAG_PRG_REJECT; never on the hot path)
 # ---------------------------------------------------------------------------
 U64_MAX = (1 << 64) - 1

@@ -33,6 +33,10 @@ file; its definition stands in ``scr_step``'s docstring.
 The COO transport of what the two compressors produce (``sparse_encode`` /
 ``sparse_decode``, ``sparse_compressor.py:234-284``) lives in
 ``sfl_amd.utils.sparse`` and is re-exported here.
+
+The quantized compressors for dense payloads (``QuantizedZeroPoint``,
+``QuantizedLSTM``, ``QuantizedFP``, ``quantized_compressor.py:65-228``) live in
+``sfl_amd.utils.quantized`` and are re-exported here too.
 """
 
 from __future__ import annotations
@@ -290,3 +294,5 @@ class SCRSparse:
 
 
 from .sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode  # noqa: E402,F401
+from .quantized import (QuantizedCompressedData, QuantizedCompressor, QuantizedFP, QuantizedLSTM,  # noqa: E402,F401
+                        QuantizedZeroPoint)

@@ -320,12 +320,15 @@ def sparse_decode(data: List) -> List:
 
 
 def payload_nbytes(payload) -> int:
-    """Bytes of a list of dense arrays, tensors, ``SparseCOO``s, or a mix."""
+    """Bytes of a list of dense arrays, tensors, ``SparseCOO``s, quantized
+    objects (``utils/quantized.py``: their codes), or a mix."""
     if payload is None:
         return 0
     if isinstance(payload, (list, tuple)):
         return sum(payload_nbytes(p) for p in payload)
-    if isinstance(payload, SparseCOO):
+    from .quantized import QuantizedCompressedData
+
+    if isinstance(payload, (SparseCOO, QuantizedCompressedData)):
         return payload.nbytes
     if isinstance(payload, torch.Tensor):
         return payload.numel() * payload.element_size()
