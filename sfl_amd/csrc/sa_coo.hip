@@ -9,8 +9,9 @@
 //             streaming division
 //
 // A non-zero is decided on the bit pattern, (bits & ~sign) != 0.  The encode
-// is a compaction in sa_stc's wave layout: every wave owns a CONTIGUOUS index
-// range, so wave order is index order; a wave's first rank is the exclusive
+// is a compaction in the wave layout that sa_stc uses too (sa_compress.h):
+// every wave owns a CONTIGUOUS index range, so wave order is index order; a
+// wave's first rank is the exclusive
 // prefix of the per-wave counts, and inside a tile a lane's rank comes from
 // three ballots over the lane counts (0..4).  No atomics and no sort: index_out
 // is strictly ascending by construction.  A payload is another party's data:
@@ -19,21 +20,14 @@
 // host or synchronised.
 #include <hip/hip_runtime.h>
 
-#include "../../include/sfl_sa.h"
-#include "sa_elems.h"
-#include "sa_internal.h"
+#include "sa_compress.h"
 
 namespace sa {
 namespace coo {
 
 using namespace sa::elems;
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTileBlock = kTile * kWaves;
-constexpr int kMaxBlocks = 1024;  // 4 resident blocks per CU on 256 CUs
-constexpr int kMaxWaves = kMaxBlocks * kWaves;
-constexpr uint64_t kMaxN = (uint64_t)1 << 31;  // the flat index is int32
+using namespace sa::wave;  // the contiguous wave layout and the block scan
+using namespace sa::entry;
 
 // scratch: the per-wave counts, then (after k_offsets) each wave's first
 // rank; one word more holds the total
@@ -51,59 +45,6 @@ struct Bits<double> {
     return ((uint64_t)__double_as_longlong(x) & 0x7fffffffffffffffull) != 0;
   }
 };
-
-// this wave's index range [lo, hi): `len` (a multiple of kTile) per wave,
-// waves in index order (sa_stc.hip's wave_range)
-struct Range {
-  uint64_t lo, hi;
-  int lane;
-};
-__device__ __forceinline__ Range wave_range(uint64_t n, uint64_t len) {
-  const uint64_t w = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-  Range r;
-  r.lo = w * len < n ? w * len : n;
-  r.hi = r.lo + len < n ? r.lo + len : n;
-  r.lane = threadIdx.x & 63;
-  return r;
-}
-
-// inclusive scan of one value per thread over the block (thread order;
-// sa_stc.hip's block_scan_incl)
-__device__ __forceinline__ uint32_t block_scan_incl(uint32_t s, uint32_t* total) {
-  __shared__ uint32_t wsum[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = s;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t v = (uint32_t)__shfl_up((int)inc, off, 64);
-    if (lane >= off) inc += v;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-  for (int i = 0; i < kWaves; i++) {
-    if (i < wave) base += wsum[i];
-    all += wsum[i];
-  }
-  *total = all;
-  return base + inc;
-}
-
-struct Grid {
-  int grid, nwaves, vec;
-  uint64_t len;
-};
-// a function of n only, so count and fill agree on every wave's range
-static Grid grid_of(uint64_t n, uintptr_t ptrs) {
-  uint64_t blocks = (n + kTileBlock - 1) / kTileBlock;
-  if (blocks > (uint64_t)kMaxBlocks) blocks = kMaxBlocks;
-  if (blocks == 0) blocks = 1;
-  Grid g;
-  g.grid = (int)blocks, g.nwaves = g.grid * kWaves;
-  g.len = (n + g.nwaves - 1) / g.nwaves;
-  g.len = (g.len + kTile - 1) / kTile * kTile;
-  g.vec = (ptrs & 15) == 0;
-  return g;
-}
 
 // --- encode -----------------------------------------------------------------
 
@@ -255,23 +196,9 @@ static int entry_grid(uint64_t nnz) {
   return (int)blocks;
 }
 
-static int check_float(int t, const char* what) {
-  if (t != SA_F32 && t != SA_F64) {
-    sa_set_error("%s: the element type must be SA_F32 or SA_F64", what);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
+static int check_type_n(int t, uint64_t n, const char* what) {
+  return check_float_n(t, n, 31, what, " (the flat index is int32)");
 }
-
-static int check_n(uint64_t n, const char* what) {
-  if (n >= kMaxN) {
-    sa_set_error("%s: n must be below 2^31 (the flat index is int32)", what);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
-static bool misaligned(const void* p, uintptr_t esz) { return ((uintptr_t)p & (esz - 1)) != 0; }
 
 // index, data and the flag record of a payload of nnz entries over n elements
 static int check_payload(const void* index, const void* data, uintptr_t esz, uint64_t nnz, uint64_t n,
@@ -293,28 +220,26 @@ static int check_payload(const void* index, const void* data, uintptr_t esz, uin
 using namespace sa::coo;
 
 extern "C" int sa_coo_scratch_bytes(uint64_t n, int x_type) {
-  int rc = check_float(x_type, "sa_coo_scratch_bytes");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_scratch_bytes");
+  const int rc = check_type_n(x_type, n, "sa_coo_scratch_bytes");
   return rc == SA_OK ? (int)kScratchBytes : rc;
 }
 
 extern "C" int sa_coo_count(const void* x, int x_type, uint64_t n, void* scratch, void* nnz_out, void* stream) {
-  int rc = check_float(x_type, "sa_coo_count");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_count");
+  const int rc = check_type_n(x_type, n, "sa_coo_count");
   if (rc != SA_OK) return rc;
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
-  if ((n && !x) || misaligned(x, esz) || !scratch || misaligned(scratch, 4) || !nnz_out || misaligned(nnz_out, 4)) {
+  if ((n && !x) || misaligned(x, elem_size(x_type)) || !scratch || misaligned(scratch, 4) || !nnz_out ||
+      misaligned(nnz_out, 4)) {
     sa_set_error("sa_coo_count: bad arguments (x, scratch and nnz_out are required; element-aligned x, "
                  "4-byte aligned scratch and nnz_out)");
     return SA_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  const Grid g = grid_of(n, (uintptr_t)x);
+  const Grid g = wave_grid(n, (uintptr_t)x);
   uint32_t* cnt = (uint32_t*)scratch;
-  if (x_type == SA_F32)
-    hipLaunchKernelGGL(k_count<float>, dim3(g.grid), dim3(kBlock), 0, s, (const float*)x, n, g.len, g.vec, cnt);
-  else
-    hipLaunchKernelGGL(k_count<double>, dim3(g.grid), dim3(kBlock), 0, s, (const double*)x, n, g.len, g.vec, cnt);
+  dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL(k_count<T>, dim3(g.grid), dim3(kBlock), 0, s, (const T*)x, n, g.len, g.vec, cnt);
+  });
   SA_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_offsets, dim3(1), dim3(kBlock), 0, s, cnt, g.nwaves, (uint32_t*)nnz_out);
   SA_HIP_CHECK(hipGetLastError());
@@ -323,10 +248,9 @@ extern "C" int sa_coo_count(const void* x, int x_type, uint64_t n, void* scratch
 
 extern "C" int sa_coo_fill(const void* x, int x_type, uint64_t n, const void* scratch, void* index_out,
                            void* data_out, uint64_t cap, void* flag, void* stream) {
-  int rc = check_float(x_type, "sa_coo_fill");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_fill");
+  const int rc = check_type_n(x_type, n, "sa_coo_fill");
   if (rc != SA_OK) return rc;
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
+  const uintptr_t esz = elem_size(x_type);
   if (cap > n) {
     sa_set_error("sa_coo_fill: cap exceeds n");
     return SA_ERR_ARG;
@@ -338,23 +262,20 @@ extern "C" int sa_coo_fill(const void* x, int x_type, uint64_t n, const void* sc
     return SA_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  const Grid g = grid_of(n, (uintptr_t)x);
-  const uint32_t* first = (const uint32_t*)scratch;
-  if (x_type == SA_F32)
-    hipLaunchKernelGGL(k_fill<float>, dim3(g.grid), dim3(kBlock), 0, s, (const float*)x, n, g.len, g.vec, first,
-                       (int32_t*)index_out, (float*)data_out, (uint32_t)cap, (uint32_t*)flag);
-  else
-    hipLaunchKernelGGL(k_fill<double>, dim3(g.grid), dim3(kBlock), 0, s, (const double*)x, n, g.len, g.vec, first,
-                       (int32_t*)index_out, (double*)data_out, (uint32_t)cap, (uint32_t*)flag);
+  const Grid g = wave_grid(n, (uintptr_t)x);
+  dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL(k_fill<T>, dim3(g.grid), dim3(kBlock), 0, s, (const T*)x, n, g.len, g.vec,
+                       (const uint32_t*)scratch, (int32_t*)index_out, (T*)data_out, (uint32_t)cap, (uint32_t*)flag);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
 
 extern "C" int sa_coo_decode(const void* index, const void* data, int x_type, uint64_t nnz, uint64_t n,
                              void* dense_out, void* flag, void* stream) {
-  int rc = check_float(x_type, "sa_coo_decode");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_decode");
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
+  int rc = check_type_n(x_type, n, "sa_coo_decode");
+  const uintptr_t esz = elem_size(x_type);
   if (rc == SA_OK) rc = check_payload(index, data, esz, nnz, n, flag, "sa_coo_decode");
   if (rc != SA_OK) return rc;
   if ((n && !dense_out) || misaligned(dense_out, esz)) {
@@ -365,12 +286,11 @@ extern "C" int sa_coo_decode(const void* index, const void* data, int x_type, ui
   hipStream_t s = (hipStream_t)stream;
   SA_HIP_CHECK(hipMemsetAsync(dense_out, 0, n * esz, s));
   if (nnz == 0) return SA_OK;
-  if (x_type == SA_F32)
-    hipLaunchKernelGGL(k_scatter<float>, dim3(entry_grid(nnz)), dim3(kBlock), 0, s, (const int32_t*)index,
-                       (const float*)data, nnz, (uint32_t)n, (float*)dense_out, (uint32_t*)flag);
-  else
-    hipLaunchKernelGGL(k_scatter<double>, dim3(entry_grid(nnz)), dim3(kBlock), 0, s, (const int32_t*)index,
-                       (const double*)data, nnz, (uint32_t)n, (double*)dense_out, (uint32_t*)flag);
+  dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL(k_scatter<T>, dim3(entry_grid(nnz)), dim3(kBlock), 0, s, (const int32_t*)index,
+                       (const T*)data, nnz, (uint32_t)n, (T*)dense_out, (uint32_t*)flag);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
@@ -378,17 +298,15 @@ extern "C" int sa_coo_decode(const void* index, const void* data, int x_type, ui
 extern "C" int sa_coo_axpy(const void* index, const void* data, int x_type, uint64_t nnz, double w, void* acc,
                            int acc_type, uint64_t n, void* flag, void* stream) {
   int rc = check_float(x_type, "sa_coo_axpy");
-  if (rc == SA_OK) rc = check_float(acc_type, "sa_coo_axpy");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_axpy");
+  if (rc == SA_OK) rc = check_type_n(acc_type, n, "sa_coo_axpy");
   if (rc != SA_OK) return rc;
   if (x_type == SA_F64 && acc_type == SA_F32) {
     sa_set_error("sa_coo_axpy: float64 data needs a float64 accumulator");
     return SA_ERR_ARG;
   }
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8, asz = acc_type == SA_F32 ? 4 : 8;
-  rc = check_payload(index, data, esz, nnz, n, flag, "sa_coo_axpy");
+  rc = check_payload(index, data, elem_size(x_type), nnz, n, flag, "sa_coo_axpy");
   if (rc != SA_OK) return rc;
-  if ((n && !acc) || misaligned(acc, asz)) {
+  if ((n && !acc) || misaligned(acc, elem_size(acc_type))) {
     sa_set_error("sa_coo_axpy: acc is required and element-aligned");
     return SA_ERR_ARG;
   }
@@ -397,6 +315,7 @@ extern "C" int sa_coo_axpy(const void* index, const void* data, int x_type, uint
   const dim3 grid(entry_grid(nnz)), block(kBlock);
   const int32_t* idx = (const int32_t*)index;
   uint32_t* f = (uint32_t*)flag;
+  // (data, accumulator): three pairs, stated one by one
   if (x_type == SA_F32 && acc_type == SA_F32)
     hipLaunchKernelGGL((k_axpy<float, float>), grid, block, 0, s, idx, (const float*)data, nnz, (uint32_t)n, (float)w,
                        (float*)acc, f);
@@ -411,22 +330,19 @@ extern "C" int sa_coo_axpy(const void* index, const void* data, int x_type, uint
 }
 
 extern "C" int sa_coo_finish(void* acc, int acc_type, uint64_t n, double divisor, void* stream) {
-  int rc = check_float(acc_type, "sa_coo_finish");
-  if (rc == SA_OK) rc = check_n(n, "sa_coo_finish");
+  const int rc = check_type_n(acc_type, n, "sa_coo_finish");
   if (rc != SA_OK) return rc;
-  const uintptr_t asz = acc_type == SA_F32 ? 4 : 8;
-  if ((n && !acc) || misaligned(acc, asz)) {
+  if ((n && !acc) || misaligned(acc, elem_size(acc_type))) {
     sa_set_error("sa_coo_finish: acc is required and element-aligned");
     return SA_ERR_ARG;
   }
   if (n == 0) return SA_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const Grid g = grid_of(n, (uintptr_t)acc);
-  if (acc_type == SA_F32)
-    hipLaunchKernelGGL(k_divide<float>, dim3(g.grid), dim3(kBlock), 0, s, (float*)acc, n, g.len, g.vec,
-                       (float)divisor);
-  else
-    hipLaunchKernelGGL(k_divide<double>, dim3(g.grid), dim3(kBlock), 0, s, (double*)acc, n, g.len, g.vec, divisor);
+  const Grid g = wave_grid(n, (uintptr_t)acc);
+  dispatch_float(acc_type, [&](auto t) {
+    typedef decltype(t) A;
+    hipLaunchKernelGGL(k_divide<A>, dim3(g.grid), dim3(kBlock), 0, (hipStream_t)stream, (A*)acc, n, g.len, g.vec,
+                       (A)divisor);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }

@@ -28,18 +28,17 @@
 // behind the head, element accesses with the same lane map otherwise.
 #include <hip/hip_runtime.h>
 
-#include "../../include/sfl_sa.h"
-#include "sa_elems.h"
-#include "sa_internal.h"
+#include "sa_compress.h"
 
 namespace sa {
 namespace quant {
 
+using namespace sa::entry;
 using sa::elems::f32x4;
 using sa::elems::f64x2;
+using sa::wave::kBlock;
+using sa::wave::kWaves;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 // the grid's bound: 2 resident blocks per CU on 256 CUs.  Measured at 100M
 // elements against 256, 1024 and 2048: the passes that
 // HBM bounds are fastest here; the fp8 decoder, which the VALU bounds, wants
@@ -49,7 +48,6 @@ constexpr int kFp8DecodeBlocks = 2 * kMaxBlocks;
 constexpr int kEncRun = 16;  // elements per lane and run, encoding: one 16-byte store of int8 codes
 template <class T>
 constexpr int kDecRun = 16 / sizeof(T);  // decoding: one 16-byte store of floats
-constexpr uint64_t kMaxN = (uint64_t)1 << 32;
 
 // scratch of the range: per block min, max and a NaN mark, as three T
 constexpr size_t kScratchBytes = (size_t)kMaxBlocks * 3 * sizeof(double);
@@ -423,24 +421,6 @@ static Plan plan_of(uint64_t n, const void* coarse, uintptr_t align, uintptr_t s
   return p;
 }
 
-static int check_float(int t, const char* what) {
-  if (t != SA_F32 && t != SA_F64) {
-    sa_set_error("%s: the element type must be SA_F32 or SA_F64", what);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
-static int check_n(uint64_t n, const char* what) {
-  if (n >= kMaxN) {
-    sa_set_error("%s: n must be below 2^32", what);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
-static bool misaligned(const void* p, uintptr_t esz) { return ((uintptr_t)p & (esz - 1)) != 0; }
-
 // the float vector and the code vector of n elements
 static int check_vectors(const void* x, uintptr_t esz, const void* q, int q_bytes, uint64_t n, const char* what) {
   if (q_bytes != 1 && q_bytes != 2) {
@@ -540,94 +520,76 @@ static void launch_range(const void* x, uint64_t n, void* scratch, void* out, hi
 using namespace sa::quant;
 
 extern "C" int sa_quant_scratch_bytes(uint64_t n, int x_type) {
-  int rc = check_float(x_type, "sa_quant_scratch_bytes");
-  if (rc == SA_OK) rc = check_n(n, "sa_quant_scratch_bytes");
+  const int rc = check_float_n(x_type, n, 32, "sa_quant_scratch_bytes");
   return rc == SA_OK ? (int)kScratchBytes : rc;
 }
 
 extern "C" int sa_quant_range(const void* x, int x_type, uint64_t n, void* scratch, void* out3, void* stream) {
-  int rc = check_float(x_type, "sa_quant_range");
-  if (rc == SA_OK) rc = check_n(n, "sa_quant_range");
+  const int rc = check_float_n(x_type, n, 32, "sa_quant_range");
   if (rc != SA_OK) return rc;
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
+  const uintptr_t esz = elem_size(x_type);
   if ((n && !x) || misaligned(x, esz) || !scratch || misaligned(scratch, 8) || !out3 || misaligned(out3, esz)) {
     sa_set_error("sa_quant_range: bad arguments (x, scratch and out3 are required; element-aligned x and out3, "
                  "8-byte aligned scratch)");
     return SA_ERR_ARG;
   }
-  if (x_type == SA_F32)
-    launch_range<float>(x, n, scratch, out3, (hipStream_t)stream);
-  else
-    launch_range<double>(x, n, scratch, out3, (hipStream_t)stream);
+  dispatch_float(x_type, [&](auto t) { launch_range<decltype(t)>(x, n, scratch, out3, (hipStream_t)stream); });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
 
 extern "C" int sa_quant_affine(const void* x, int x_type, uint64_t n, int mode, double p0, double p1, int qmin,
                                int qmax, void* q_out, int q_bytes, void* stream) {
-  int rc = check_float(x_type, "sa_quant_affine");
-  if (rc == SA_OK) rc = check_n(n, "sa_quant_affine");
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
-  if (rc == SA_OK) rc = check_vectors(x, esz, q_out, q_bytes, n, "sa_quant_affine");
+  int rc = check_float_n(x_type, n, 32, "sa_quant_affine");
+  if (rc == SA_OK) rc = check_vectors(x, elem_size(x_type), q_out, q_bytes, n, "sa_quant_affine");
   if (rc == SA_OK) rc = check_mode(mode, "sa_quant_affine");
   if (rc == SA_OK) rc = check_clamp(qmin, qmax, q_bytes, "sa_quant_affine");
   if (rc != SA_OK) return rc;
   if (n == 0) return SA_OK;
-  if (x_type == SA_F32)
-    launch_affine<float>(true, x, n, mode, p0, p1, qmin, qmax, q_out, q_bytes, (hipStream_t)stream);
-  else
-    launch_affine<double>(true, x, n, mode, p0, p1, qmin, qmax, q_out, q_bytes, (hipStream_t)stream);
+  dispatch_float(x_type, [&](auto t) {
+    launch_affine<decltype(t)>(true, x, n, mode, p0, p1, qmin, qmax, q_out, q_bytes, (hipStream_t)stream);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
 
 extern "C" int sa_dequant_affine(const void* q, int q_bytes, uint64_t n, int mode, double p0, double p1, int x_type,
                                  void* out, void* stream) {
-  int rc = check_float(x_type, "sa_dequant_affine");
-  if (rc == SA_OK) rc = check_n(n, "sa_dequant_affine");
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
-  if (rc == SA_OK) rc = check_vectors(out, esz, q, q_bytes, n, "sa_dequant_affine");
+  int rc = check_float_n(x_type, n, 32, "sa_dequant_affine");
+  if (rc == SA_OK) rc = check_vectors(out, elem_size(x_type), q, q_bytes, n, "sa_dequant_affine");
   if (rc == SA_OK) rc = check_mode(mode, "sa_dequant_affine");
   if (rc != SA_OK) return rc;
   if (n == 0) return SA_OK;
-  if (x_type == SA_F32)
-    launch_affine<float>(false, out, n, mode, p0, p1, 0, 0, (void*)q, q_bytes, (hipStream_t)stream);
-  else
-    launch_affine<double>(false, out, n, mode, p0, p1, 0, 0, (void*)q, q_bytes, (hipStream_t)stream);
+  dispatch_float(x_type, [&](auto t) {
+    launch_affine<decltype(t)>(false, out, n, mode, p0, p1, 0, 0, (void*)q, q_bytes, (hipStream_t)stream);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
 
 extern "C" int sa_quant_fp8(const void* x, int x_type, uint64_t n, double scale, int mant_len, int exp_offset,
                             void* q_out, void* stream) {
-  int rc = check_float(x_type, "sa_quant_fp8");
-  if (rc == SA_OK) rc = check_n(n, "sa_quant_fp8");
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
-  if (rc == SA_OK) rc = check_vectors(x, esz, q_out, 1, n, "sa_quant_fp8");
+  int rc = check_float_n(x_type, n, 32, "sa_quant_fp8");
+  if (rc == SA_OK) rc = check_vectors(x, elem_size(x_type), q_out, 1, n, "sa_quant_fp8");
   if (rc == SA_OK) rc = check_fp8(mant_len, exp_offset, "sa_quant_fp8");
   if (rc != SA_OK) return rc;
   if (n == 0) return SA_OK;
-  if (x_type == SA_F32)
-    launch_fp8<float>(true, x, n, scale, mant_len, q_out, (hipStream_t)stream);
-  else
-    launch_fp8<double>(true, x, n, scale, mant_len, q_out, (hipStream_t)stream);
+  dispatch_float(x_type,
+                 [&](auto t) { launch_fp8<decltype(t)>(true, x, n, scale, mant_len, q_out, (hipStream_t)stream); });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }
 
 extern "C" int sa_dequant_fp8(const void* q, uint64_t n, double scale, int mant_len, int exp_offset, int x_type,
                               void* out, void* stream) {
-  int rc = check_float(x_type, "sa_dequant_fp8");
-  if (rc == SA_OK) rc = check_n(n, "sa_dequant_fp8");
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
-  if (rc == SA_OK) rc = check_vectors(out, esz, q, 1, n, "sa_dequant_fp8");
+  int rc = check_float_n(x_type, n, 32, "sa_dequant_fp8");
+  if (rc == SA_OK) rc = check_vectors(out, elem_size(x_type), q, 1, n, "sa_dequant_fp8");
   if (rc == SA_OK) rc = check_fp8(mant_len, exp_offset, "sa_dequant_fp8");
   if (rc != SA_OK) return rc;
   if (n == 0) return SA_OK;
-  if (x_type == SA_F32)
-    launch_fp8<float>(false, out, n, scale, mant_len, (void*)q, (hipStream_t)stream);
-  else
-    launch_fp8<double>(false, out, n, scale, mant_len, (void*)q, (hipStream_t)stream);
+  dispatch_float(x_type, [&](auto t) {
+    launch_fp8<decltype(t)>(false, out, n, scale, mant_len, (void*)q, (hipStream_t)stream);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }

@@ -21,17 +21,16 @@
 // stay in device memory.
 #include <hip/hip_runtime.h>
 
-#include "../../include/sfl_sa.h"
-#include "sa_elems.h"
-#include "sa_internal.h"
+#include "sa_compress.h"
 
 namespace sa {
 namespace scr {
 
 using namespace sa::elems;
+using namespace sa::entry;
+using sa::wave::kBlock;
+using sa::wave::kWaves;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 constexpr uint32_t kSeg = 8 * kTile;         // elements of a row per wave (form, apply)
 constexpr uint32_t kSpan = kBlock * kEpl;    // positions of the row per block (column sums)
 constexpr uint32_t kWide = 64;               // rows from this length on take the wave-per-segment kernels
@@ -385,10 +384,7 @@ static int launch(const T* a, const T* b, const T* r, uint32_t R, uint32_t C, ui
 
 // SA_OK with the shape's layout, or SA_ERR_ARG with the error set
 static int check_shape(const char* who, uint64_t R, uint64_t C, uint64_t K, int x_type, Layout* y) {
-  if (x_type != SA_F32 && x_type != SA_F64) {
-    sa_set_error("%s: x_type must be SA_F32 or SA_F64", who);
-    return SA_ERR_ARG;
-  }
+  if (check_float(x_type, who, "x_type") != SA_OK) return SA_ERR_ARG;
   if (R == 0 || C == 0 || K == 0) {
     sa_set_error("%s: rows, cols and inner must be positive", who);
     return SA_ERR_ARG;
@@ -422,7 +418,7 @@ extern "C" int sa_scr(const void* a, const void* b, const void* r, int x_type, u
   Layout y;
   const int rc = check_shape("sa_scr", rows, cols, inner, x_type, &y);
   if (rc != SA_OK) return rc;
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
+  const uintptr_t esz = elem_size(x_type);
   const uintptr_t all = (uintptr_t)a | (uintptr_t)b | (uintptr_t)r | (uintptr_t)sparse_out | (uintptr_t)res_out;
   if (!a || !sparse_out || !scratch || (all & (esz - 1)) || ((uintptr_t)stats_out & 3) ||
       ((uintptr_t)scratch & 7)) {
@@ -435,12 +431,9 @@ extern "C" int sa_scr(const void* a, const void* b, const void* r, int x_type, u
     sa_set_error("sa_scr: only res_out may alias r");
     return SA_ERR_ARG;
   }
-  hipStream_t s = (hipStream_t)stream;
-  if (x_type == SA_F32)
-    return launch<float>((const float*)a, (const float*)b, (const float*)r, (uint32_t)rows, (uint32_t)cols,
-                         (uint32_t)inner, threshold, (float*)sparse_out, (float*)res_out, (uint32_t*)stats_out,
-                         (char*)scratch, s);
-  return launch<double>((const double*)a, (const double*)b, (const double*)r, (uint32_t)rows, (uint32_t)cols,
-                        (uint32_t)inner, threshold, (double*)sparse_out, (double*)res_out, (uint32_t*)stats_out,
-                        (char*)scratch, s);
+  return dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    return launch((const T*)a, (const T*)b, (const T*)r, (uint32_t)rows, (uint32_t)cols, (uint32_t)inner, threshold,
+                  (T*)sparse_out, (T*)res_out, (uint32_t*)stats_out, (char*)scratch, (hipStream_t)stream);
+  });
 }

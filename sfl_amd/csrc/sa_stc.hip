@@ -19,20 +19,15 @@
 // or synchronised; threshold, tie quota and mu never leave the device.
 #include <hip/hip_runtime.h>
 
-#include "../../include/sfl_sa.h"
-#include "sa_elems.h"
-#include "sa_internal.h"
+#include "sa_compress.h"
 
 namespace sa {
 namespace stc {
 
 using namespace sa::elems;
+using namespace sa::wave;  // the contiguous wave layout and the block scan
+using namespace sa::entry;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTileBlock = kTile * kWaves;
-constexpr int kMaxBlocks = 1024;  // 4 resident blocks per CU on 256 CUs
-constexpr int kMaxWaves = kMaxBlocks * kWaves;
 constexpr int kMaxBins = 2048;
 // LDS copies of the histogram: lane l adds into copy l % 4, so lanes of one
 // wave-instruction that share a digit (the first pass's digit is the
@@ -71,21 +66,6 @@ struct Key<double> {
   }
   static __device__ __forceinline__ double value(uint64_t k) { return __longlong_as_double((long long)k); }
 };
-
-// this wave's index range [lo, hi): `len` (a multiple of kTile) per wave,
-// waves in index order
-struct Range {
-  uint64_t lo, hi;
-  int lane;
-};
-__device__ __forceinline__ Range wave_range(uint64_t n, uint64_t len) {
-  const uint64_t w = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-  Range r;
-  r.lo = w * len < n ? w * len : n;
-  r.hi = r.lo + len < n ? r.lo + len : n;
-  r.lane = threadIdx.x & 63;
-  return r;
-}
 
 // --- the block's histogram in LDS ---------------------------------------
 __device__ __forceinline__ void hist_clear(uint32_t* h) {
@@ -194,26 +174,6 @@ __global__ void __launch_bounds__(kBlock) k_hist(const T* __restrict__ u, uint64
     }
   }
   hist_flush(h, hist, nbins);
-}
-
-// inclusive scan of one value per thread over the block (thread order)
-__device__ __forceinline__ uint32_t block_scan_incl(uint32_t s, uint32_t* total) {
-  __shared__ uint32_t wsum[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = s;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t v = (uint32_t)__shfl_up((int)inc, off, 64);
-    if (lane >= off) inc += v;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-  for (int i = 0; i < kWaves; i++) {
-    if (i < wave) base += wsum[i];
-    all += wsum[i];
-  }
-  *total = all;
-  return base + inc;
 }
 
 // One block: the bin that holds rank k; prefix |= bin << shift, k -= the
@@ -398,14 +358,8 @@ static int launch(const T* a, const T* b, const T* r, uint64_t n, uint64_t mask_
   const int npass = sizeof(T) == 4 ? 3 : 6;
 
   // the grid is a function of n only: the survivors' sum has one order
-  uint64_t blocks = (n + kTileBlock - 1) / kTileBlock;
-  if (blocks > (uint64_t)kMaxBlocks) blocks = kMaxBlocks;
-  const int grid = (int)blocks, nwaves = grid * kWaves;
-  uint64_t len = (n + nwaves - 1) / nwaves;
-  len = (len + kTile - 1) / kTile * kTile;
-  const uintptr_t all = (uintptr_t)a | (uintptr_t)b | (uintptr_t)r | (uintptr_t)sparse | (uintptr_t)res |
-                        (uintptr_t)acc;
-  const int vec = (all & 15) == 0;
+  const auto [grid, nwaves, vec, len] = wave_grid(
+      n, (uintptr_t)a | (uintptr_t)b | (uintptr_t)r | (uintptr_t)sparse | (uintptr_t)res | (uintptr_t)acc);
 
   // mask_num 0: threshold key 0 with quota 0 masks nothing; mask_num n: a
   // threshold above every key masks everything; neither needs the select
@@ -449,34 +403,23 @@ static int launch(const T* a, const T* b, const T* r, uint64_t n, uint64_t mask_
 using namespace sa::stc;
 
 extern "C" int sa_stc_scratch_bytes(uint64_t n, int x_type) {
-  if (x_type != SA_F32 && x_type != SA_F64) {
-    sa_set_error("sa_stc_scratch_bytes: x_type must be SA_F32 or SA_F64");
-    return SA_ERR_ARG;
-  }
-  if (n >> 32) {
-    sa_set_error("sa_stc_scratch_bytes: n must be below 2^32");
-    return SA_ERR_ARG;
-  }
-  return (int)kScratchBytes;
+  int rc = check_float(x_type, "sa_stc_scratch_bytes", "x_type");
+  if (rc == SA_OK) rc = check_n(n, 32, "sa_stc_scratch_bytes");
+  return rc == SA_OK ? (int)kScratchBytes : rc;
 }
 
 extern "C" int sa_stc(const void* a, const void* b, const void* r, int x_type, uint64_t n, uint64_t mask_num,
                       void* sparse_out, void* res_out, void* acc_inout, void* mu_out, void* scratch,
                       void* stream) {
-  if (x_type != SA_F32 && x_type != SA_F64) {
-    sa_set_error("sa_stc: x_type must be SA_F32 or SA_F64");
-    return SA_ERR_ARG;
-  }
-  if (n >> 32) {
-    sa_set_error("sa_stc: n must be below 2^32 (ranks and counts are 32-bit)");
-    return SA_ERR_ARG;
-  }
+  int rc = check_float(x_type, "sa_stc", "x_type");
+  if (rc == SA_OK) rc = check_n(n, 32, "sa_stc", " (ranks and counts are 32-bit)");
+  if (rc != SA_OK) return rc;
   if (mask_num > n) {
     sa_set_error("sa_stc: mask_num exceeds n");
     return SA_ERR_ARG;
   }
   if (n == 0) return SA_OK;
-  const uintptr_t esz = x_type == SA_F32 ? 4 : 8;
+  const uintptr_t esz = elem_size(x_type);
   const uintptr_t all = (uintptr_t)a | (uintptr_t)b | (uintptr_t)r | (uintptr_t)sparse_out | (uintptr_t)res_out |
                         (uintptr_t)acc_inout | (uintptr_t)mu_out;
   if (!a || !sparse_out || !res_out || !scratch || (all & (esz - 1)) || ((uintptr_t)scratch & 7)) {
@@ -489,10 +432,9 @@ extern "C" int sa_stc(const void* a, const void* b, const void* r, int x_type, u
     sa_set_error("sa_stc: only res_out may alias r");
     return SA_ERR_ARG;
   }
-  hipStream_t s = (hipStream_t)stream;
-  if (x_type == SA_F32)
-    return launch<float>((const float*)a, (const float*)b, (const float*)r, n, mask_num, (float*)sparse_out,
-                         (float*)res_out, (float*)acc_inout, (float*)mu_out, (char*)scratch, s);
-  return launch<double>((const double*)a, (const double*)b, (const double*)r, n, mask_num, (double*)sparse_out,
-                        (double*)res_out, (double*)acc_inout, (double*)mu_out, (char*)scratch, s);
+  return dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    return launch((const T*)a, (const T*)b, (const T*)r, n, mask_num, (T*)sparse_out, (T*)res_out, (T*)acc_inout,
+                  (T*)mu_out, (char*)scratch, (hipStream_t)stream);
+  });
 }

@@ -495,16 +495,35 @@ def hb_normals(words: torch.Tensor, sigma: float, out: torch.Tensor) -> torch.Te
 
 
 # ---------------------------------------------------------------------------
+# the compression kernels (sa_stc, sa_scr, sa_coo_*, sa_quant_*): what their
+# wrappers share
+# ---------------------------------------------------------------------------
+def _float_xtype(what: str, dtype) -> int:
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: float32 or float64, not {dtype}")
+    return xtype_of(dtype)
+
+
+def _scratch_bytes(what: str, entry: str, dims: Sequence[int], dtype) -> int:
+    """The library's ``entry(*dims, x_type)``: bytes of device scratch."""
+    xt = _float_xtype(what, dtype)
+    rc = getattr(L.lib(), entry)(*(int(d) for d in dims), xt)
+    if rc < 0:
+        L.check(rc, entry)
+    return rc
+
+
+def _require_scratch(what: str, scratch: torch.Tensor, need: int, sized_by: str) -> None:
+    if scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"{what}: scratch smaller than {sized_by}")
+
+
+# ---------------------------------------------------------------------------
 # sparse ternary compression (sa_stc; fed_stc's worker and server halves)
 # ---------------------------------------------------------------------------
 def stc_scratch_bytes(n: int, dtype: torch.dtype) -> int:
     """Bytes of device scratch ``stc`` needs for ``n`` elements of ``dtype``."""
-    if dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"stc: float32 or float64, not {dtype}")
-    rc = L.lib().sa_stc_scratch_bytes(int(n), xtype_of(dtype))
-    if rc < 0:
-        L.check(rc, "sa_stc_scratch_bytes")
-    return rc
+    return _scratch_bytes("stc", "sa_stc_scratch_bytes", (n,), dtype)
 
 
 def stc(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, mask_num: int, sparse_out: torch.Tensor,
@@ -522,8 +541,7 @@ def stc(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, mask_nu
             raise ValueError("stc: contiguous tensors of one dtype and size")
     if mu_out is not None and (mu_out.dtype != a.dtype or mu_out.numel() < 1):
         raise ValueError("stc: mu_out is one element of the data's dtype")
-    if scratch.numel() * scratch.element_size() < stc_scratch_bytes(n, a.dtype):
-        raise ValueError("stc: scratch smaller than stc_scratch_bytes(n, dtype)")
+    _require_scratch("stc", scratch, stc_scratch_bytes(n, a.dtype), "stc_scratch_bytes(n, dtype)")
     if not 0 <= int(mask_num) <= n:
         raise ValueError("stc: mask_num outside [0, n]")
     L.check(L.lib().sa_stc(_ptr(a), _ptr(b), _ptr(r), xtype_of(a.dtype), n, int(mask_num), _ptr(sparse_out),
@@ -537,13 +555,8 @@ def stc(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, mask_nu
 # ---------------------------------------------------------------------------
 def scr_scratch_bytes(shape3: Sequence[int], dtype: torch.dtype) -> int:
     """Bytes of device scratch ``scr`` needs for a ``[rows, cols, inner]`` tensor of ``dtype``."""
-    if dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"scr: float32 or float64, not {dtype}")
-    rows, cols, inner = (int(d) for d in shape3)
-    rc = L.lib().sa_scr_scratch_bytes(rows, cols, inner, xtype_of(dtype))
-    if rc < 0:
-        L.check(rc, "sa_scr_scratch_bytes")
-    return rc
+    rows, cols, inner = shape3
+    return _scratch_bytes("scr", "sa_scr_scratch_bytes", (rows, cols, inner), dtype)
 
 
 def scr(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, shape3: Sequence[int], threshold: float,
@@ -566,8 +579,8 @@ def scr(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, shape3:
     if stats_out is not None and (stats_out.element_size() != 4 or stats_out.numel() < 2
                                   or not stats_out.is_contiguous()):
         raise ValueError("scr: stats_out is two 32-bit integers")
-    if scratch.numel() * scratch.element_size() < scr_scratch_bytes((rows, cols, inner), a.dtype):
-        raise ValueError("scr: scratch smaller than scr_scratch_bytes(shape3, dtype)")
+    _require_scratch("scr", scratch, scr_scratch_bytes((rows, cols, inner), a.dtype),
+                     "scr_scratch_bytes(shape3, dtype)")
     L.check(L.lib().sa_scr(_ptr(a), _ptr(b), _ptr(r), xtype_of(a.dtype), rows, cols, inner, float(threshold),
                            _ptr(sparse_out), _ptr(res_out), _ptr(stats_out), _ptr(scratch),
                            C.c_void_p(_stream(a))),
@@ -579,22 +592,13 @@ def scr(a: torch.Tensor, b: torch.Tensor | None, r: torch.Tensor | None, shape3:
 # COO transport and the sparse server sum (sa_coo_*; utils/sparse.py and
 # SparsePlainAggregator on top)
 # ---------------------------------------------------------------------------
-_COO_FLOATS = (torch.float32, torch.float64)
-
-
-def _coo_float(what: str, dtype) -> int:
-    if dtype not in _COO_FLOATS:
-        raise TypeError(f"{what}: float32 or float64, not {dtype}")
-    return xtype_of(dtype)
-
-
 def _coo_words(what: str, name: str, t: torch.Tensor, words: int) -> None:
     if t.dtype != torch.int32 or t.numel() < words or not t.is_contiguous():
         raise ValueError(f"{what}: {name} is {words} contiguous int32 word{'s' if words > 1 else ''}")
 
 
 def _coo_payload(what: str, index: torch.Tensor, data: torch.Tensor) -> int:
-    xt = _coo_float(what, data.dtype)
+    xt = _float_xtype(what, data.dtype)
     if index.dtype != torch.int32 or index.dim() != 1 or data.dim() != 1 or index.numel() != data.numel() \
             or not index.is_contiguous() or not data.is_contiguous():
         raise ValueError(f"{what}: index (int32) and data are flat contiguous tensors of one length")
@@ -603,11 +607,7 @@ def _coo_payload(what: str, index: torch.Tensor, data: torch.Tensor) -> int:
 
 def coo_scratch_bytes(n: int, dtype: torch.dtype) -> int:
     """Bytes of device scratch ``coo_count`` / ``coo_fill`` need for ``n`` elements of ``dtype``."""
-    xt = _coo_float("coo_scratch_bytes", dtype)
-    rc = L.lib().sa_coo_scratch_bytes(int(n), xt)
-    if rc < 0:
-        L.check(rc, "sa_coo_scratch_bytes")
-    return rc
+    return _scratch_bytes("coo_scratch_bytes", "sa_coo_scratch_bytes", (n,), dtype)
 
 
 def coo_flag(device) -> torch.Tensor:
@@ -624,12 +624,11 @@ def coo_count(x: torch.Tensor, scratch: torch.Tensor, nnz_out: torch.Tensor) -> 
     first rank into ``scratch`` for ``coo_fill``.  See sa_coo_count in
     include/sfl_sa.h."""
     _require_gpu(x, scratch, nnz_out)
-    xt = _coo_float("coo_count", x.dtype)
+    xt = _float_xtype("coo_count", x.dtype)
     if not x.is_contiguous():
         raise ValueError("coo_count: a contiguous tensor")
     _coo_words("coo_count", "nnz_out", nnz_out, 1)
-    if scratch.numel() * scratch.element_size() < coo_scratch_bytes(x.numel(), x.dtype):
-        raise ValueError("coo_count: scratch smaller than coo_scratch_bytes(n, dtype)")
+    _require_scratch("coo_count", scratch, coo_scratch_bytes(x.numel(), x.dtype), "coo_scratch_bytes(n, dtype)")
     L.check(L.lib().sa_coo_count(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(nnz_out), C.c_void_p(_stream(x))),
             "sa_coo_count")
     return nnz_out
@@ -643,7 +642,7 @@ def coo_fill(x: torch.Tensor, scratch: torch.Tensor, index_out: torch.Tensor, da
     are stored; a count other than ``cap`` sets ``SA_COO_BAD_COUNT`` in
     ``flag``."""
     _require_gpu(x, scratch, index_out, data_out, flag)
-    xt = _coo_float("coo_fill", x.dtype)
+    xt = _float_xtype("coo_fill", x.dtype)
     if not x.is_contiguous():
         raise ValueError("coo_fill: a contiguous tensor")
     if data_out.dtype != x.dtype:
@@ -653,8 +652,7 @@ def coo_fill(x: torch.Tensor, scratch: torch.Tensor, index_out: torch.Tensor, da
     cap = index_out.numel() if cap is None else int(cap)
     if not 0 <= cap <= min(index_out.numel(), x.numel()):
         raise ValueError("coo_fill: cap outside [0, min(len(index_out), n)]")
-    if scratch.numel() * scratch.element_size() < coo_scratch_bytes(x.numel(), x.dtype):
-        raise ValueError("coo_fill: scratch smaller than coo_scratch_bytes(n, dtype)")
+    _require_scratch("coo_fill", scratch, coo_scratch_bytes(x.numel(), x.dtype), "coo_scratch_bytes(n, dtype)")
     L.check(L.lib().sa_coo_fill(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(index_out), _ptr(data_out), cap,
                                 _ptr(flag), C.c_void_p(_stream(x))), "sa_coo_fill")
 
@@ -680,7 +678,7 @@ def coo_axpy(index: torch.Tensor, data: torch.Tensor, w: float, acc: torch.Tenso
     float64; float64 data: float64).  Validates like ``coo_decode``."""
     _require_gpu(index, data, acc, flag)
     xt = _coo_payload("coo_axpy", index, data)
-    at = _coo_float("coo_axpy", acc.dtype)
+    at = _float_xtype("coo_axpy", acc.dtype)
     if data.dtype == torch.float64 and acc.dtype == torch.float32:
         raise TypeError("coo_axpy: float64 data needs a float64 accumulator")
     if not acc.is_contiguous():
@@ -696,7 +694,7 @@ def coo_axpy(index: torch.Tensor, data: torch.Tensor, w: float, acc: torch.Tenso
 def coo_finish(acc: torch.Tensor, divisor: float) -> torch.Tensor:
     """acc[i] = acc[i] / A(divisor) in place."""
     _require_gpu(acc)
-    at = _coo_float("coo_finish", acc.dtype)
+    at = _float_xtype("coo_finish", acc.dtype)
     if not acc.is_contiguous():
         raise ValueError("coo_finish: a contiguous accumulator")
     L.check(L.lib().sa_coo_finish(_ptr(acc), at, acc.numel(), float(divisor), C.c_void_p(_stream(acc))),
@@ -713,7 +711,7 @@ _QUANT_CODES = {torch.int8: 1, torch.int16: 2}
 def _quant_pair(what: str, x: torch.Tensor, q: torch.Tensor, codes=_QUANT_CODES) -> tuple[int, int]:
     """(x_type, q_bytes) of a float tensor and its codes: contiguous, one length, one device."""
     _require_gpu(x, q)
-    xt = _coo_float(what, x.dtype)
+    xt = _float_xtype(what, x.dtype)
     if q.dtype not in codes:
         raise TypeError(f"{what}: the codes are {' or '.join(str(d) for d in codes)}, not {q.dtype}")
     if not x.is_contiguous() or not q.is_contiguous() or x.numel() != q.numel() or x.device != q.device:
@@ -723,24 +721,20 @@ def _quant_pair(what: str, x: torch.Tensor, q: torch.Tensor, codes=_QUANT_CODES)
 
 def quant_scratch_bytes(n: int, dtype: torch.dtype) -> int:
     """Bytes of device scratch ``quant_range`` needs for ``n`` elements of ``dtype``."""
-    xt = _coo_float("quant_scratch_bytes", dtype)
-    rc = L.lib().sa_quant_scratch_bytes(int(n), xt)
-    if rc < 0:
-        L.check(rc, "sa_quant_scratch_bytes")
-    return rc
+    return _scratch_bytes("quant_scratch_bytes", "sa_quant_scratch_bytes", (n,), dtype)
 
 
 def quant_range(x: torch.Tensor, scratch: torch.Tensor, out3: torch.Tensor) -> torch.Tensor:
     """``out3 = (min, max, max|x|)`` of ``x``, three elements of its dtype on
     the device, NaN-propagating.  See sa_quant_range in include/sfl_sa.h."""
     _require_gpu(x, scratch, out3)
-    xt = _coo_float("quant_range", x.dtype)
+    xt = _float_xtype("quant_range", x.dtype)
     if not x.is_contiguous():
         raise ValueError("quant_range: a contiguous tensor")
     if out3.dtype != x.dtype or out3.numel() < 3 or not out3.is_contiguous():
         raise ValueError("quant_range: out3 is three contiguous elements of the data's dtype")
-    if scratch.numel() * scratch.element_size() < quant_scratch_bytes(x.numel(), x.dtype):
-        raise ValueError("quant_range: scratch smaller than quant_scratch_bytes(n, dtype)")
+    _require_scratch("quant_range", scratch, quant_scratch_bytes(x.numel(), x.dtype),
+                     "quant_scratch_bytes(n, dtype)")
     L.check(L.lib().sa_quant_range(_ptr(x), xt, x.numel(), _ptr(scratch), _ptr(out3), C.c_void_p(_stream(x))),
             "sa_quant_range")
     return out3
