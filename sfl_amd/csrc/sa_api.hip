@@ -101,12 +101,12 @@ struct LaunchArgs {
   //   sign -1: u gets -m = t + (1 - K);    v gets +m = -t + (K - 1)
   bool stream(int slot, const sa_pcg64& g, int sign, int u, int v = -1) {
     if (!valid_sign(sign)) return false;
-    StreamArg& s = a.s[slot];
+    StreamSeed& s = a.seed[slot];
     s.s_lo = g.state.lo;
     s.s_hi = g.state.hi;
     s.inc_lo = g.inc.lo;
     s.inc_hi = g.inc.hi;
-    s.smask = sign < 0 ? ~0ULL : 0ULL;
+    if (sign < 0) a.sub_mask |= 1u << slot;
     const uint64_t fold = sign > 0 ? kMaskOffset : 1 - kMaskOffset;
     a.c[u].bias += fold;
     if (v >= 0) a.c[v].bias -= fold;

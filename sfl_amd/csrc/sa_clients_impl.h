@@ -17,9 +17,12 @@
 // interleaved asm block from sa_draw2.h) and the lane draws both of its
 // elements for a group back to back, so a group's constants (inc, inc*G_J,
 // sign mask) serve two draws per stream.  They are scalar-loaded from the
-// kernarg segment into SGPRs, group g+1's loads issued after group g's first
-// draw (latency hidden under one draw; SMEM returns out of order, so the
-// wait is lgkmcnt(0) right before g+1 starts).  No VGPRs or LDS traffic go
+// kernarg segment into SGPRs, laid out by group (sa_internal.h, GroupArg):
+// two 16-dword loads per group -- the first draw's addends, dead after it,
+// and the second draw's with the sign masks -- group g+1's issued after
+// group g's first draw (latency hidden under one draw; SMEM returns out of
+// order, so the wait is lgkmcnt(0) right before g+1 starts) and group 0's
+// with the tile's other loads at its top.  No VGPRs or LDS traffic go
 // to constants; the multiplier limbs (A, A^J) sit in 8 wave-uniform VGPRs.
 // Measured on the draw alone (tools/microbench/draw_issue.hip): LDS-resident
 // constants issue 10-15 % slower than SGPR ones.
@@ -335,10 +338,12 @@ __device__ __forceinline__ uint32_t vreg(uint32_t x) {
       [u] "+v"(u), [k1] "=&s"(k1), [k2] "=&s"(k2), [k3] "=&s"(k3)
 // Operand classes: the multiplier limbs are wave-uniform VGPRs (set once per
 // launch), the stream constants SGPRs (scalar-loaded per stream and tile), so
-// every VOP3 reads at most one SGPR (the gfx9 constant-bus limit).
+// every VOP3 reads at most one SGPR (the gfx9 constant-bus limit).  mm: the
+// sign mask as 64 bits (0 or ~0, as StreamArg holds it), the compare's
+// operand; the v_bitop3s take its low word.
 #define SA_PCG_DRAW_INS                                                                  \
   [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [c0] "s"(inc.w0),                    \
-      [c1] "s"(inc.w1), [c23] "s"(inc.hi), [m] "s"(m), [mm] "s"((uint64_t)m << 32 | m)
+      [c1] "s"(inc.w1), [c23] "s"(inc.hi), [m] "s"((uint32_t)mm), [mm] "s"(mm)
 #define SA_PCG_DRAW_CLOBBERS \
   "vcc", "scc", "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9"
 
@@ -349,7 +354,7 @@ __device__ __forceinline__ uint32_t vreg(uint32_t x) {
 // mask of raw == 0 draws (an SGPR pair; 0 at the tile's start).
 __device__ __forceinline__ void pcg_draw_pair(uint32_t& s0, uint32_t& s1, uint32_t& s2, uint32_t& s3, uint32_t a0,
                                               uint32_t a1, uint32_t a2, uint32_t a3, const Inc& inc,
-                                              uint32_t m, uint64_t& zs, uint64_t& u, uint64_t& v) {
+                                              uint64_t mm, uint64_t& zs, uint64_t& u, uint64_t& v) {
   uint64_t k1, k2, k3;
   uint32_t vlo = (uint32_t)v, vhi = (uint32_t)(v >> 32);
   asm volatile(SA_PCG_DRAW_ASM
@@ -364,7 +369,7 @@ __device__ __forceinline__ void pcg_draw_pair(uint32_t& s0, uint32_t& s1, uint32
 }
 __device__ __forceinline__ void pcg_draw_pair_a(uint32_t& s0, uint32_t& s1, uint32_t& s2, uint32_t& s3, uint32_t a0,
                                                 uint32_t a1, uint32_t a2, uint32_t a3, const Inc& inc,
-                                                uint32_t m, uint64_t& zs, uint64_t& u, uint64_t& v) {
+                                                uint64_t mm, uint64_t& zs, uint64_t& u, uint64_t& v) {
   uint64_t k1, k2, k3;
   asm volatile(SA_PCG_DRAW_ASM
                "v_lshl_add_u64 %[u], v[6:7], 0, %[u]\n\t"
@@ -375,7 +380,7 @@ __device__ __forceinline__ void pcg_draw_pair_a(uint32_t& s0, uint32_t& s1, uint
 }
 __device__ __forceinline__ void pcg_draw_one(uint32_t& s0, uint32_t& s1, uint32_t& s2, uint32_t& s3, uint32_t a0,
                                              uint32_t a1, uint32_t a2, uint32_t a3, const Inc& inc,
-                                             uint32_t m, uint64_t& zs, uint64_t& u) {
+                                             uint64_t mm, uint64_t& zs, uint64_t& u) {
   uint64_t k1, k2, k3;
   asm volatile(SA_PCG_DRAW_ASM
                "v_lshl_add_u64 %[u], v[6:7], 0, %[u]"
@@ -563,23 +568,43 @@ constexpr int clients_waves(int P, int L) {
 }
 
 typedef __attribute__((address_space(4))) const uint64_t* kptr_t;
-static_assert(offsetof(StreamArg, inc_hi) == 24 && offsetof(StreamArg, cj_hi) == 40 &&
-                  offsetof(StreamArg, smask) == 48 && offsetof(StreamArg, inc_w0) == 64 &&
-                  offsetof(StreamArg, cj_w0) == 80,
-              "StreamArg layout (scalar loads below)");
+static_assert(sizeof(GroupJump) == 64 && sizeof(GroupStep) == 64 && offsetof(KArgs, g) % 64 == 0 &&
+                  offsetof(GroupArg, step) == 64 && offsetof(GroupJump, b) == 24 && offsetof(GroupStep, b) == 24 &&
+                  offsetof(GroupStep, ma) == 48 && sizeof(StreamAdd) == sizeof(Inc),
+              "GroupArg layout (two 16-dword scalar loads per group: kload below)");
+static_assert(offsetof(KArgs, cx) % 64 == 0 && offsetof(KArgs, cbias) % 64 == 0 && kMaxLocal == 8,
+              "KArgs::cx / cbias: one 16-dword scalar load each");
 
 typedef __attribute__((address_space(4))) const KArgs kargs_t;
+
+// N (2, 4 or 8) consecutive u64 of the kernarg image, aligned to their
+// size, in ONE scalar load (s_load_dwordx4 / x8 / x16): a half of a draw
+// group's GroupArg (N = 8), or the head of the clients' cx array.
+template <int N>
+struct KVec {
+  typedef uint64_t type __attribute__((ext_vector_type(N)));
+};
+template <int N>
+__device__ __forceinline__ typename KVec<N>::type kload(const __attribute__((address_space(4))) void* p) {
+  return *(const __attribute__((address_space(4))) typename KVec<N>::type*)p;
+}
 
 // The kernarg image through an opaque SGPR pointer: loads through it are
 // scalar loads that cannot be hoisted above the fence, so per-client values
 // (buffer bases, bias, weight) are re-read where they are used instead of
 // pinning ~100 SGPRs (descriptors, biases, weights of 8 clients) across the
-// whole tile loop.
+// whole tile loop.  One fenced pointer serves a whole phase of the tile (the
+// loads at the top, the mask expansion, the finish): each fenced_args() is an
+// s_mov_b64 of the kernarg pointer.  refence() renews the fence on such a
+// pointer in place (no instruction: the old value dies there); the loads
+// after it stay behind the asm blocks before it, which is what keeps the
+// mask expansion's per-group fetches where they are written.
 __device__ __forceinline__ kargs_t* fenced_args() {
   kargs_t* p = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
   return p;
 }
+__device__ __forceinline__ void refence(kargs_t*& p) { asm volatile("" : "+s"(p)); }
 
 template <typename XT, typename CT, int L, int X, int K = kAllPairs>
 __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::count + L * X, L))
@@ -631,15 +656,24 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
     }
     const Jump jl = compose(kLaneJump.e[threadIdx.x], jb);
     const u128 aji = ld128(a.aji_lo, a.aji_hi);
-#pragma unroll
-    for (int j = 0; j < P; j++) {
-      const StreamArg& s = a.s[j];
-      const u128 sf = apply(jl, ld128(s.s_lo, s.s_hi), ld128(s.inc_lo, s.inc_hi));
-      const u128 v = aji * (sf - ld128(s.cj_lo, s.cj_hi));
-      st[j].p01 = lo64(v);
-      st[j].s2 = (uint32_t)hi64(v);
-      st[j].s3 = (uint32_t)(hi64(v) >> 32);
-    }
+    // per stream: state, increment and the low half of inc * G_J from its
+    // seed, the high half from the stream's place in its draw group
+    for_each_index([&](auto gc) {
+      constexpr int g = decltype(gc)::value;
+      constexpr Group G = SchedOf<L, X, K>::value.g[g];
+#define SA_PARK(j, h)                                                                         \
+  {                                                                                           \
+    const StreamSeed& s = a.seed[j];                                                          \
+    const u128 sf = apply(jl, ld128(s.s_lo, s.s_hi), ld128(s.inc_lo, s.inc_hi));              \
+    const u128 v = aji * (sf - ld128(s.cj_lo, a.g[g].jump.h.hi));                             \
+    st[j].p01 = lo64(v);                                                                      \
+    st[j].s2 = (uint32_t)hi64(v);                                                             \
+    st[j].s3 = (uint32_t)(hi64(v) >> 32);                                                     \
+  }
+      SA_PARK(G.qa, a)
+      if constexpr (G.qb >= 0) SA_PARK(G.qb, b)
+#undef SA_PARK
+    }, std::make_integer_sequence<int, SchedOf<L, X, K>::value.n>{});
   }
   // multiplier limbs: jump (first element of a tile) and plain step
   uint32_t mj[4], mp[4];
@@ -705,18 +739,56 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
     Vec2<CT> wv[kGeneral ? L : 1];
     Vec2<uint64_t> pv[kGeneral ? L : 1];
     uint64_t acc[kE][L];  // per-client accumulators (negated<L> clients: -acc)
+    // The constants of the NEXT group of the mask expansion below: two
+    // 16-dword scalar loads (GroupArg: the first draw's addends, the second
+    // draw's and the sign masks), and the start values of the accumulators
+    // that group touches first (KArgs::cbias).
+    using SO = SchedOf<L, X, K>;  // the schedule (a static constexpr: usable in the lambdas)
+    static_assert(SO::value.n <= kMaxGroups, "the schedule's draw groups fit KArgs::g");
+    Inc ni[2], nj[2];  // plain-step / tile-jump addends
+    uint64_t nm[2];    // sign masks, 64 bits
+    uint64_t nb[4];    // first-touch start values of ua, va, ub, vb
+    auto fetch = [&](kargs_t* kp, auto gc) __attribute__((always_inline)) {
+      constexpr int g = decltype(gc)::value;
+      constexpr Group G = SO::value.g[g];
+      const auto J = kload<8>(&kp->g[g].jump);
+      const auto S = kload<8>(&kp->g[g].step);
+      nj[0] = Inc{J[0], J[1], J[2]};
+      nj[1] = Inc{J[3], J[4], J[5]};
+      ni[0] = Inc{S[0], S[1], S[2]};
+      ni[1] = Inc{S[3], S[4], S[5]};
+      nm[0] = S[6];
+      nm[1] = S[7];
+      if constexpr ((G.F & 1) != 0) nb[0] = kp->cbias[G.ua];
+      if constexpr ((G.F & 2) != 0) nb[1] = kp->cbias[G.va];
+      if constexpr ((G.F & 4) != 0) nb[2] = kp->cbias[G.ub];
+      if constexpr ((G.F & 8) != 0) nb[3] = kp->cbias[G.vb];
+    };
     {
+      // everything the tile needs before its first draw in one batch of
+      // scalar loads and one wait: the clients' input pointers, group 0's
+      // stream constants; then the tile's buffer loads
       kargs_t* ka = fenced_args();
       const bool cont = kGeneral && ka->continue_mode;
+      constexpr bool kMasksOnly = (K & (kBipartite | kCrossOnly)) != 0;  // the values enter elsewhere
+      const void* xp[L];
+      if constexpr (!kMasksOnly && L > 1) {
+        const auto v = kload<(L <= 2 ? 2 : L <= 4 ? 4 : 8)>(ka->cx);
+#pragma unroll
+        for (int c = 0; c < L; c++) xp[c] = (const void*)v[c];
+      } else {
+        xp[0] = kMasksOnly ? nullptr : ka->cx[0];
+      }
+      if constexpr (P > 0) fetch(ka, std::integral_constant<int, 0>{});
 #pragma unroll
       for (int c = 0; c < L; c++) {
         if (SA_ABLATE & 8) {
 #pragma unroll
           for (int k = 0; k < kE; k++) xv[c].v[k] = (XT)(int)(i + k + c);
-        } else if constexpr ((K & (kBipartite | kCrossOnly)) != 0) {  // masks only: the values enter elsewhere
+        } else if constexpr (kMasksOnly) {
           xv[c].v[0] = xv[c].v[1] = (XT)0;
         } else {
-          xv[c] = bload2<XT>(make_rsrc(ka->c[c].x, cont ? 0 : n * sizeof(XT)), i);
+          xv[c] = bload2<XT>(make_rsrc(xp[c], cont ? 0 : n * sizeof(XT)), i);
         }
         if constexpr (kGeneral) {
           const void* wp = ka->c[c].wvec;
@@ -727,8 +799,8 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
         // clients: X - bias, see negated<L>): written by the client's first
         // draw (first-touch variants), preset here only where the schedule
         // cannot (Sched::preset)
-        if ((SchedOf<L, X, K>::value.preset >> c) & 1) {
-          const uint64_t bias = negated<L>(c) ? (uint64_t)X - ka->c[c].bias : ka->c[c].bias;
+        if ((SO::value.preset >> c) & 1) {
+          const uint64_t bias = ka->cbias[c];
 #pragma unroll
           for (int k = 0; k < kE; k++) acc[k][c] = bias;
         }
@@ -749,40 +821,21 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
       zs[k] = 0;
     }
     if constexpr (P > 0) {
-      using SO = SchedOf<L, X, K>;  // the schedule (a static constexpr: usable in the lambdas)
-      Inc ni[2], nj[2];  // next group's plain-step / tile-jump addends
-      uint32_t nm[2];
-      auto fetch = [&](int g) {
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int q = h == 0 ? SO::value.g[g].qa : SO::value.g[g].qb;
-          if (q < 0) continue;
-          kptr_t c = (const kptr_t)(&fenced_args()->s[q]);
-          ni[h] = Inc{c[8], c[9], c[3]};
-          nj[h] = Inc{c[10], c[11], c[5]};
-          nm[h] = (uint32_t)c[6] ^ ((h == 0 ? SO::value.g[g].fa : SO::value.g[g].fb) ? 0xFFFFFFFFu : 0u);
-        }
-      };
-      // a first-touched accumulator starts from its client's bias (SGPRs)
-      auto bias_of = [&](int c) -> uint64_t {
-        if (c < 0) return 0;
-        kargs_t* ka = fenced_args();
-        return negated<L>(c) ? (uint64_t)X - ka->c[c].bias : ka->c[c].bias;
-      };
-      fetch(0);
+      kargs_t* kx = fenced_args();  // the phase's kernarg pointer, re-fenced in place before each fetch
       for_each_index([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         constexpr Group G = SO::value.g[g];
         Inc ci[2], cj[2];
-        uint32_t m[2];
+        uint64_t m[2];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
           ci[h] = ni[h];
           cj[h] = nj[h];
           m[h] = nm[h];
         }
-        const uint64_t bua = (G.F & 1) ? bias_of(G.ua) : 0, bva = (G.F & 2) ? bias_of(G.va) : 0;
-        const uint64_t bub = (G.F & 4) ? bias_of(G.ub) : 0, bvb = (G.F & 8) ? bias_of(G.vb) : 0;
+        // a first-touched accumulator starts from its client's bias (SGPRs)
+        const uint64_t bua = (G.F & 1) ? nb[0] : 0, bva = (G.F & 2) ? nb[1] : 0;
+        const uint64_t bub = (G.F & 4) ? nb[2] : 0, bvb = (G.F & 8) ? nb[3] : 0;
 #pragma unroll
         for (int k = 0; k < kE; k++) {
           const uint32_t* mk = k == 0 ? mj : mp;
@@ -820,7 +873,12 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
               pcg_draw2_one<G.F>(sa.p01, sa.s2, sa.s3, sb.p01, sb.s2, sb.s3, mk[0], mk[1], mk[2], mk[3], ia, m[0],
                                  ib, m[1], zh[k], ak[G.ua], ak[G.ub], bua, bub);
           }
-          if (k == 0 && g + 1 < SO::value.n && !(SA_ABLATE & 128)) fetch(g + 1);
+          if constexpr (g + 1 < SO::value.n && !(SA_ABLATE & 128)) {
+            if (k == 0) {
+              refence(kx);
+              fetch(kx, std::integral_constant<int, g + 1>{});
+            }
+          }
         }
       }, std::make_integer_sequence<int, SO::value.n>{});
     }
@@ -1028,14 +1086,19 @@ int launch_clients(const KArgs& in, void* stream) {
       a.dp_block0 += off / kDpBlock;
       const Jump jo = jump_of(off);
       for (int j = 0; j < P; j++) {
-        const u128 s = apply(jo, mk128(a.s[j].s_hi, a.s[j].s_lo), mk128(a.s[j].inc_hi, a.s[j].inc_lo));
-        a.s[j].s_lo = lo64(s);
-        a.s[j].s_hi = hi64(s);
+        const u128 s = apply(jo, mk128(a.seed[j].s_hi, a.seed[j].s_lo), mk128(a.seed[j].inc_hi, a.seed[j].inc_lo));
+        a.seed[j].s_lo = lo64(s);
+        a.seed[j].s_hi = hi64(s);
       }
     }
     a.masked_mask = 0;
-    for (int c = 0; c < L; c++)
+    for (int c = 0; c < L; c++) {
       if (a.c[c].masked_out) a.masked_mask |= 1u << c;
+      // the tile top's arrays: input pointers, and the accumulators' start
+      // values (a negated client's accumulator holds X - bias, see negated<L>)
+      a.cx[c] = a.c[c].x;
+      a.cbias[c] = negated<L>(c) ? (uint64_t)X - a.c[c].bias : a.c[c].bias;
+    }
     const uint64_t tiles = (a.n + kTile - 1) / kTile;
     const int grid = (int)(tiles < (uint64_t)maxb ? tiles : (uint64_t)maxb);
     if (grid >= (1 << kGridBits)) {
@@ -1049,14 +1112,24 @@ int launch_clients(const KArgs& in, void* stream) {
     const u128 aji = inv128(jj.mult);
     a.aji_lo = lo64(aji);
     a.aji_hi = hi64(aji);
-    for (int j = 0; j < P; j++) {
-      const u128 cj = jj.gsum * mk128(a.s[j].inc_hi, a.s[j].inc_lo);
-      a.s[j].cj_lo = lo64(cj);
-      a.s[j].cj_hi = hi64(cj);
-      a.s[j].inc_w0 = (uint32_t)a.s[j].inc_lo;
-      a.s[j].inc_w1 = a.s[j].inc_lo >> 32;
-      a.s[j].cj_w0 = (uint32_t)a.s[j].cj_lo;
-      a.s[j].cj_w1 = a.s[j].cj_lo >> 32;
+    // the streams' constants by draw group (GroupArg): inc, inc * G_J and
+    // the sign mask, inverted for a negated client's cross stream
+    const auto& sched = SchedOf<L, X, K>::value;
+    for (int g = 0; g < sched.n; g++) {
+      const Group& G = sched.g[g];
+      for (int h = 0; h < 2; h++) {
+        const int j = h == 0 ? G.qa : G.qb;
+        if (j < 0) continue;
+        const u128 inc = mk128(a.seed[j].inc_hi, a.seed[j].inc_lo);
+        const u128 cj = jj.gsum * inc;
+        StreamAdd& step = h == 0 ? a.g[g].step.a : a.g[g].step.b;
+        StreamAdd& jump = h == 0 ? a.g[g].jump.a : a.g[g].jump.b;
+        step = StreamAdd{(uint32_t)lo64(inc), lo64(inc) >> 32, hi64(inc)};
+        jump = StreamAdd{(uint32_t)lo64(cj), lo64(cj) >> 32, hi64(cj)};
+        a.seed[j].cj_lo = lo64(cj);
+        const bool sub = ((a.sub_mask >> j) & 1) != (h == 0 ? G.fa : G.fb);
+        (h == 0 ? a.g[g].step.ma : a.g[g].step.mb) = sub ? ~0ull : 0ull;
+      }
     }
     hipLaunchKernelGGL((k_clients<XT, CT, L, X, K>), dim3(grid), dim3(kBlockThreads), 0,
                        (hipStream_t)stream, a);

@@ -45,6 +45,7 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 constexpr int kSumMaxIn = 32;    // inputs per launch of the server sums (sa_server.hip)
 constexpr int kMaxLocal = 8;     // co-located clients per fused launch
 constexpr int kMaxStreams = 32;  // mask streams per launch (kernel-arg resident)
+constexpr int kMaxGroups = 16;   // draw groups per launch (every instantiated schedule fits: checked in the kernel)
 constexpr int kMaskPass = 16;    // streams per pass of the single-client kernel
 constexpr int kBipartiteClients = 8;  // sa_fused_bipartite: two quads, their 16 cross pairs
 
@@ -78,15 +79,41 @@ constexpr int kCrossCounts[] = {32, 24, 16, 8, 4, 2, 1};
 
 
 // Kernel-argument image (lives in the kernarg segment; read with scalar loads).
-struct StreamArg {
+//
+// A stream's increment as the draw's three SGPR addends (sa_draw2.h's Inc):
+// the low half's two 32-bit words zero-extended, and the high half.
+struct StreamAdd {
+  uint64_t w0, w1, hi;
+};
+// Everything the tile loop reads of the streams, laid out by draw GROUP of the
+// launch's schedule (sa_clients_impl.h, Sched: two streams per asm block, a
+// and b; b unused for a single draw), so that one group costs two 16-dword
+// scalar loads per tile and no other scalar work: `jump` holds what the
+// lane's first draw of a tile reads (the merged tile jump's addends, inc *
+// G_J) and is dead after it, `step` the second draw's (the increment) and
+// the two sign masks.  Filled by the launcher, which knows the schedule.
+struct alignas(64) GroupJump {
+  StreamAdd a, b;
+  uint64_t pad[2];
+};
+struct alignas(64) GroupStep {
+  StreamAdd a, b;
+  // 0 (the draw is added) or ~0 (subtracted), the flip of a negated
+  // client's cross stream folded in: the 64-bit operand of the raw == 0
+  // compare, whose low word the draw's v_bitop3s take
+  uint64_t ma, mb;
+};
+struct GroupArg {
+  GroupJump jump;
+  GroupStep step;
+};
+// The rest of a stream: what the caller supplies (sa_api.hip's args builder)
+// and, from the launcher, the low half of inc * G_J.  Read by the kernel's
+// prologue only.
+struct StreamSeed {
   uint64_t s_lo, s_hi;      // generator state before draw 0 of this call
   uint64_t inc_lo, inc_hi;  // PCG64 increment
-  uint64_t cj_lo, cj_hi;    // inc * G_J: constant part of the per-tile jump
-  uint64_t smask;           // 0 (stream added) or ~0 (stream subtracted)
-  uint64_t pad;
-  // the draw's addends (filled by the launcher): inc_lo's and cj_lo's two
-  // 32-bit words, zero-extended
-  uint64_t inc_w0, inc_w1, cj_w0, cj_w1;
+  uint64_t cj_lo;           // inc * G_J, low half (the high half: GroupJump's hi)
 };
 
 struct ClientArg {
@@ -101,7 +128,14 @@ struct ClientArg {
 
 struct KArgs {
   ClientArg c[kMaxLocal];
-  StreamArg s[kMaxStreams];
+  // the tile top's view of the clients, each array one scalar load (filled
+  // by the launcher): the input vectors, and the accumulators' start values
+  // (c[].bias; X - c[].bias for a client the kernel keeps negated)
+  alignas(64) const void* cx[kMaxLocal];
+  alignas(64) uint64_t cbias[kMaxLocal];
+  GroupArg g[kMaxGroups];
+  StreamSeed seed[kMaxStreams];
+  uint32_t sub_mask;  // bit j set iff stream j is subtracted (sign -1)
   uint64_t n;
   uint64_t aj_lo, aj_hi;    // A^J, J = grid stride - 1 (merged tile jump)
   uint64_t aji_lo, aji_hi;  // (A^J)^-1 mod 2^128 (prologue: park states one jump back)

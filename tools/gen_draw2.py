@@ -33,6 +33,12 @@ would read two SGPRs (bias and borrow), one more than the gfx9 constant bus
 allows; the kernel's schedule orders groups so that no client is first
 touched as a subtracting partner (and presets any that would be).
 
+SGPRs: each stream keeps two carry pairs (k2: kO, c2, the acc_v borrow; k3:
+the discarded carry-outs, c1, and for stream b the raw == 0 compare's lane
+mask, stream a's going to VCC) -- four pairs per block -- and takes its sign
+mask as 64 bits (0 or ~0), the compare's operand as the kernel loads it; the
+v_bitop3s read the pair's low word.
+
 The s0 / s1 operands are declared as inputs although the pair-writing mad
 overwrites their registers: the inline-asm contract has no way to say "the
 low half of that 64-bit operand", so correctness rests on the register
@@ -135,7 +141,7 @@ ROT64_STEPS = [  # replaces {cmp} .. {cnd_hi} of DRAW (the rotation), zero test 
 ROTS_STEPS = [  # replaces {cmp} .. {cnd_hi} and the zero test of DRAW; accumulate kept in place
     ("v_lshrrev_b32_e32 v{v2}, 26, %[{s3}]", set(), set()),
     ("v_xor_b32_e32 v{v3}, 63, v{v2}", set(), set()),
-    ("{zcmp}", {"z"}, set()),
+    ("{zcmp}", {"z", "k3"}, set()),
     ("v_lshrrev_b64 v[{v4}:{v5}], v{v2}, v[{v0}:{v1}]", set(), set()),
     ("v_lshlrev_b64 v[{v6}:{v7}], v{v3}, v[{v0}:{v1}]", set(), set()),
     ("{zor}", set(), {"z"}),
@@ -172,7 +178,7 @@ def draw_steps():
 def stream(tag, base, vmode, acc_u, acc_v):
     """vmode: None (no second client), "s" (subtract) or "a" (add)."""
     f = {"s0": f"s0{tag}", "s1": f"s1{tag}", "s2": f"s2{tag}", "s3": f"s3{tag}",
-         "k1": f"k1{tag}", "k2": f"k2{tag}", "k3": f"k3{tag}",
+         "k1": f"k3{tag}", "k2": f"k2{tag}", "k3": f"k3{tag}",  # k1 (a discarded carry-out) shares k3's pair
          "c0": f"c0{tag}", "c1": f"c1{tag}", "c23": f"c23{tag}", "m": f"m{tag}", "u": acc_u}
     for i in range(10):
         f[f"v{i}"] = str(base + i)
@@ -180,8 +186,9 @@ def stream(tag, base, vmode, acc_u, acc_v):
         f["zcmp"] = f"v_cmp_eq_u64_e32 vcc, %[mma], v[{base}:{base + 1}]"
         f["zor"] = "s_or_b64 %[zh], %[zh], vcc"
     else:
-        f["zcmp"] = f"v_cmp_eq_u64_e64 %[swb], %[mmb], v[{base}:{base + 1}]"
-        f["zor"] = "s_or_b64 %[zh], %[zh], %[swb]"
+        # stream b's compare mask goes to its k3 pair, dead by then (VCC is stream a's)
+        f["zcmp"] = f"v_cmp_eq_u64_e64 %[k3b], %[mmb], v[{base}:{base + 1}]"
+        f["zor"] = "s_or_b64 %[zh], %[zh], %[k3b]"
     if tag == "a":
         f["cmp"] = f"v_cmp_gt_i32_e32 vcc, 0, %[s3a]"
         f["cnd_lo"] = f"v_cndmask_b32_e32 v{base + 6}, v{base + 4}, v{base + 5}, vcc"
@@ -297,7 +304,8 @@ def block(vma, vmb, same_acc, f):
                 '[p01b] "+v"(p01b)', '[s2b] "+v"(s2b)', '[s3b] "+v"(s3b)', zout]
     outs += [f'[{x}] "=&v"({x})' if first[x] else f'[{x}] "+v"({x})' for x in accs if x in u64]
     outs += [f'[{x}{h}] "+v"({x}{h})' for x in split for h in ("lo", "hi")]
-    outs += [f'[{k}] "=&s"({k})' for k in ("k1a", "k2a", "k3a", "k1b", "k2b", "k3b", "swb")]
+    # SGPR pairs of carries: 4, or 5 with the alignbit / rot64 forms' swap mask
+    outs += [f'[{k}] "=&s"({k})' for k in ("k2a", "k3a", "k2b", "k3b") + (() if ROTS else ("swb",))]
     ins = ['[a0] "v"(a0)', '[a1] "v"(a1)', '[a2] "v"(a2)', '[a3] "v"(a3)',
            '[c0a] "s"(ia.w0)', '[c1a] "s"(ia.w1)', '[c23a] "s"(ia.hi)', '[ma] "s"(ma)',
            '[c0b] "s"(ib.w0)', '[c1b] "s"(ib.w1)', '[c23b] "s"(ib.hi)', '[mb] "s"(mb)']
@@ -322,14 +330,14 @@ def emit(name, vma, vmb, same_acc):
                   "uint32_t& s0b", "uint32_t& s1b", "uint32_t& s2b", "uint32_t& s3b"])
     params = st_params + [
               "uint32_t a0", "uint32_t a1", "uint32_t a2", "uint32_t a3",
-              "const Inc& ia", "uint32_t ma", "const Inc& ib", "uint32_t mb",
+              "const Inc& ia", "uint64_t mma", "const Inc& ib", "uint64_t mmb",
               "ZeroAcc& zh"] + [f"uint64_t& {x}" for x in accs] + [f"uint64_t b{x}" for x in accs]
     lines.append("template <int F>")
     lines.append(f"__device__ __forceinline__ void {name}(" + ", ".join(params) + ") {")
-    lines.append("  uint64_t k1a, k2a, k3a, k1b, k2b, k3b, swb;")
-    if ROTS and not ZMIN_FORM:
-        lines.append("  // the sign masks as SGPR pairs (m:m) for the 64-bit raw == 0 compare")
-        lines.append("  const uint64_t mma = (uint64_t)ma << 32 | ma, mmb = (uint64_t)mb << 32 | mb;")
+    lines.append("  uint64_t k2a, k3a, k2b, k3b;" if ROTS else "  uint64_t k2a, k3a, k2b, k3b, swb;")
+    lines.append("  // the sign masks arrive as 64 bits (0 or ~0, the SGPR pair the raw == 0 compare")
+    lines.append("  // reads); the v_bitop3s take the pair's low word")
+    lines.append("  const uint32_t ma = (uint32_t)mma, mb = (uint32_t)mmb;")
     for x in split:
         lines.append(f"  uint32_t {x}lo = (uint32_t){x}, {x}hi = (uint32_t)({x} >> 32);")
     for x in accs:

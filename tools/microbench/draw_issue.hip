@@ -189,12 +189,12 @@ __global__ void __launch_bounds__(256) k_dual(uint64_t* out, int iters, uint32_t
     for (int g = 0; g < S.n; g++) {
       const Group G = S.g[g];
       const Inc ia = ninc[0], ib = ninc[1];
-      const uint32_t ma = (uint32_t)nm[0], mb = (uint32_t)nm[1];
+      const uint64_t ma = nm[0], mb = nm[1];  // 64-bit sign masks, as the kernel passes them
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         MbState& sa = st[G.qa];
         uint64_t* ak = acc2[k];
-        const uint32_t fma_ = ma ^ (G.fa ? 0xFFFFFFFFu : 0u), fmb_ = mb ^ (G.fb ? 0xFFFFFFFFu : 0u);
+        const uint64_t fma_ = G.fa ? ~ma : ma, fmb_ = G.fb ? ~mb : mb;
         if (G.qb < 0) {
           uint32_t s0 = (uint32_t)sa.p01, s1 = (uint32_t)(sa.p01 >> 32);
           if (G.va >= 0 && G.va_add)
@@ -284,12 +284,12 @@ __global__ void __launch_bounds__(256, W) k_dualE(uint64_t* out, int iters, uint
     for (int g = 0; g < S.n; g++) {
       const Group G = S.g[g];
       const Inc ia = ninc[0], ib = ninc[1];
-      const uint32_t ma = (uint32_t)nm[0], mb = (uint32_t)nm[1];
+      const uint64_t ma = nm[0], mb = nm[1];  // 64-bit sign masks, as the kernel passes them
 #pragma unroll
       for (int k = 0; k < E; k++) {
         MbState& sa = st[G.qa];
         uint64_t* ak = acc2[k];
-        const uint32_t fma_ = ma ^ (G.fa ? 0xFFFFFFFFu : 0u), fmb_ = mb ^ (G.fb ? 0xFFFFFFFFu : 0u);
+        const uint64_t fma_ = G.fa ? ~ma : ma, fmb_ = G.fb ? ~mb : mb;
         if (G.qb < 0) {
           uint32_t s0 = (uint32_t)sa.p01, s1 = (uint32_t)(sa.p01 >> 32);
           if (G.va >= 0 && G.va_add)
@@ -419,12 +419,12 @@ __global__ void __launch_bounds__(256) k_draws(uint64_t* out, int iters, uint32_
     st[j][3] = ~tid;
   }
   Inc rinc[MODE == 0 ? P : 1];
-  uint32_t rm[MODE == 0 ? P : 1];
+  uint64_t rm[MODE == 0 ? P : 1];
   if constexpr (MODE == 0) {
 #pragma unroll
     for (int j = 0; j < P; j++) {
       rinc[j] = Inc{(uint32_t)sl[j].inc_lo, sl[j].inc_lo >> 32, sl[j].inc_hi};
-      rm[j] = (uint32_t)sl[j].smask;
+      rm[j] = sl[j].smask;
     }
   }
   uint64_t acc1[L];
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(256) k_draws(uint64_t* out, int iters, uint32_
 #pragma unroll
     for (int q = 0; q < P; q++) {
       Inc cinc;
-      uint32_t sm;
+      uint64_t sm;
       if constexpr (MODE == 0) {
         cinc = rinc[q];
         sm = rm[q];
@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(256) k_draws(uint64_t* out, int iters, uint32_
         typedef __attribute__((address_space(3))) const uint64_t* lds_u64;
         const lds_u64 cp = (lds_u64)(slp + q);
         cinc = Inc{(uint32_t)cp[0], cp[0] >> 32, cp[1]};
-        sm = (uint32_t)slp[q].smask;
+        sm = slp[q].smask;
       }
       if constexpr (PAIRS) {
         constexpr int PI = Pairs<L>::count;
