@@ -7,8 +7,8 @@
 
 #include "../../include/sfl_sa.h"
 #include "pcg128.h"
+#include "sa_elems.h"
 #include "sa_internal.h"
-#include "sa_tiles.h"
 #include "sa_philox.h"
 
 namespace sa {
@@ -21,7 +21,7 @@ namespace sa {
 // final step -- whose device-wide fence costs ~45 us -- were slower).  The
 // grid depends on n only, so the partials, and the float64 sum, are the
 // same on every board and every run.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using elems::f32x4;
 constexpr int kSumsqUnroll = 2;
 
 __device__ __forceinline__ double sq4(f32x4 v) {
@@ -89,22 +89,6 @@ struct DpArgs {
   uint64_t key, block0;
 };
 
-// Grid-stride form (SA_DP_TILE = 0; the tile form below replaced it):
-// x' = x * scale + N(0, sigma^2) / updates, 4 elements (one Philox block)
-// per lane and block; kDpUnroll blocks per lane and trip, their 16-byte
-// loads issued before the noise is formed.  With the libm Box-Muller, 2
-// blocks in flight won (0.154 vs 0.164 ms at 100M); with the hardware
-// transcendentals and bitop3 Philox, 1 block does (0.173-0.177 vs 0.186 for
-// 2 and 0.197-0.200 for 4 on one box, tools/r05_dpu.sh,
-// profiles/r05/dp_unroll_ab.txt).  Non-temporal accesses beat plain ones
-// (0.165-0.170 vs 0.176-0.178 ms) and a grid of 2x or 4x the occupancy did
-// not help (profiles/r05/dp_forms_ab.txt; SA_DP_PLAIN_MEM, SA_DP_GRID_MULT
-// select those forms for such A/Bs).
-#ifndef SA_DP_UNROLL
-#define SA_DP_UNROLL 1
-#endif
-constexpr int kDpUnroll = SA_DP_UNROLL;
-
 template <bool kPow2>
 __device__ __forceinline__ f32x4 dp_apply4(f32x4 v, float scale, const Normal4& z, const DpArgs& a) {
   f32x4 o;
@@ -115,77 +99,37 @@ __device__ __forceinline__ f32x4 dp_apply4(f32x4 v, float scale, const Normal4& 
   return o;
 }
 
-template <bool kPow2>
-__device__ __forceinline__ void dp_perturb_body(const DpArgs& a) {
-  const float scale = dp_scale(a.sumsq, a.sumsq_layer, a.clip);
-  const uint64_t nb = (a.n + 3) / 4;
-  const uint64_t full = a.n / 4;  // blocks with 4 elements
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(a.x);
-  f32x4* o4 = reinterpret_cast<f32x4*>(a.out);
-  uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; b + (kDpUnroll - 1) * stride < full; b += kDpUnroll * stride) {
-    f32x4 v[kDpUnroll];
-#pragma unroll
-    for (int u = 0; u < kDpUnroll; u++) {
-#ifdef SA_DP_PLAIN_MEM
-      v[u] = x4[b + u * stride];
-#else
-      v[u] = __builtin_nontemporal_load(x4 + b + u * stride);
-#endif
-    }
-    // keep every load ahead of the noise (the scheduler otherwise sinks the
-    // second load below the first block's Philox rounds)
-#ifndef SA_DP_NO_SCHED_BARRIER
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-    for (int u = 0; u < kDpUnroll; u++) {
-      const Normal4 z = gauss4(a.key, a.block0 + b + u * stride);
-#ifdef SA_DP_PLAIN_MEM
-      o4[b + u * stride] = dp_apply4<kPow2>(v[u], scale, z, a);
-#else
-      __builtin_nontemporal_store(dp_apply4<kPow2>(v[u], scale, z, a), o4 + b + u * stride);
-#endif
-    }
-  }
-  for (; b < nb; b += stride) {
-    const Normal4 z = gauss4(a.key, a.block0 + b);
-    if (b < full) {
-      o4[b] = dp_apply4<kPow2>(x4[b], scale, z, a);
-    } else {
-      const uint64_t e = b * 4;
-      for (int k = 0; e + k < a.n; k++)
-        a.out[e + k] = dp_apply_t<kPow2>(a.x[e + k], scale, z.z[k], a.sigma, a.updates, a.inv);
-    }
-  }
-}
-
-// Tile form (SA_DP_TILE = T > 0, the product's with T = 1): no grid stride;
-// a workgroup owns T * 256 consecutive Philox blocks, lane t blocks t,
-// t + 256, ...  The grid is ceil(blocks / (256 T)), so every workgroup
-// streams once and retires (the streaming shape that reached 0.77 of HBM for
-// a copy, profiles/r05/stream_rate.jsonl "tile").  At 100M: 0.142-0.144 ms
-// (0.70 of HBM) for T = 1, 0.148 for 2, 0.157 for 4, against 0.171-0.174 ms
-// for the occupancy-sized grid-stride form (SA_DP_TILE = 0,
-// profiles/r05/dp_tile_ab.txt).
-#ifndef SA_DP_TILE
-#define SA_DP_TILE 1
-#endif
-constexpr int kDpTile = SA_DP_TILE;
+// x' = x * scale + N(0, sigma^2) / updates, 4 elements (one Philox block)
+// per 16-byte non-temporal load and store, the loads issued before the noise
+// is formed.  No grid stride: a workgroup owns T * 256 consecutive Philox
+// blocks, lane t blocks t, t + 256, ..., and the grid is
+// ceil(blocks / (256 T)), so every workgroup streams once and retires (the
+// streaming shape that reached 0.77 of HBM for a copy,
+// profiles/r05/stream_rate.jsonl "tile").  The product's T is 1: at 100M
+// 0.142-0.144 ms (0.70 of HBM), against 0.148 ms for T = 2, 0.157 for 4 and
+// 0.171-0.174 ms for an occupancy-sized grid-stride loop
+// (profiles/r05/dp_tile_ab.txt).  In that loop, more than one block in
+// flight per lane, plain instead of non-temporal accesses and a grid of 2x
+// or 4x the occupancy lost as well (profiles/r05/dp_unroll_ab.txt,
+// dp_forms_ab.txt).  The loops over T stay although each runs once: written
+// without them the kernel has the same instructions in other registers, and
+// this form is the one that was measured.
+constexpr int kDpTile = 1;
 
 template <bool kPow2, int T>
 __device__ __forceinline__ void dp_perturb_tile(const DpArgs& a) {
   const float scale = dp_scale(a.sumsq, a.sumsq_layer, a.clip);
   const uint64_t nb = (a.n + 3) / 4;
-  const uint64_t full = a.n / 4;
+  const uint64_t full = a.n / 4;  // blocks with 4 elements
   const f32x4* x4 = reinterpret_cast<const f32x4*>(a.x);
   f32x4* o4 = reinterpret_cast<f32x4*>(a.out);
-  const uint64_t b0 = (uint64_t)stream_tile() * (256 * T) + threadIdx.x;
+  const uint64_t b0 = (uint64_t)blockIdx.x * (256 * T) + threadIdx.x;
   if (b0 + (uint64_t)(T - 1) * 256 < full) {
     f32x4 v[T];
 #pragma unroll
     for (int u = 0; u < T; u++) v[u] = __builtin_nontemporal_load(x4 + b0 + u * 256);
+    // keep every load ahead of the noise (the scheduler otherwise sinks it
+    // below the Philox rounds)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < T; u++) {
@@ -209,17 +153,10 @@ __device__ __forceinline__ void dp_perturb_tile(const DpArgs& a) {
 }
 
 __global__ void __launch_bounds__(256) k_dp_perturb(const DpArgs a) {
-  if constexpr (kDpTile > 0) {
-    if (a.inv != 0.0f)
-      dp_perturb_tile<true, kDpTile>(a);
-    else
-      dp_perturb_tile<false, kDpTile>(a);
-  } else {
-    if (a.inv != 0.0f)  // uniform: num_updates a power of two, multiply by its exact reciprocal
-      dp_perturb_body<true>(a);
-    else
-      dp_perturb_body<false>(a);
-  }
+  if (a.inv != 0.0f)  // uniform: num_updates a power of two, multiply by its exact reciprocal
+    dp_perturb_tile<true, kDpTile>(a);
+  else
+    dp_perturb_tile<false, kDpTile>(a);
 }
 
 }  // namespace sa
@@ -227,16 +164,14 @@ __global__ void __launch_bounds__(256) k_dp_perturb(const DpArgs a) {
 using namespace sa;
 
 static bool dp_ok(const sa_dp* dp, const char* who) {
-  if (!dp || !dp->sumsq || !(dp->num_updates > 0.0f) || (dp->counter0 & 3)) {
-    sa_set_error("%s: bad sa_dp (sumsq set, num_updates > 0, counter0 %% 4 == 0 required)", who);
-    return false;
-  }
-  return true;
+  if (dp_fields_ok(dp)) return true;
+  sa_set_error("%s: bad sa_dp (sumsq set, num_updates > 0, counter0 %% 4 == 0 required)", who);
+  return false;
 }
 
 extern "C" int sa_sumsq_f32(const float* x, uint64_t n, double* partials, double* sumsq, int accumulate,
                             void* stream) {
-  if ((n > 0 && !x) || !partials || !sumsq || ((uintptr_t)x & 15)) {  // n == 0: x unread, *sumsq (+)= 0
+  if ((n > 0 && !x) || !partials || !sumsq || !aligned16(x)) {  // n == 0: x unread, *sumsq (+)= 0
     sa_set_error("sa_sumsq_f32: bad arguments (x must be 16-byte aligned)");
     return SA_ERR_ARG;
   }
@@ -254,7 +189,7 @@ extern "C" int sa_sumsq_f32(const float* x, uint64_t n, double* partials, double
 }
 
 extern "C" int sa_dp_perturb_f32(const float* x, uint64_t n, const sa_dp* dp, float* out, void* stream) {
-  if ((n > 0 && (!x || !out)) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) {
+  if ((n > 0 && (!x || !out)) || !aligned16(x) || !aligned16(out)) {
     sa_set_error("sa_dp_perturb_f32: bad arguments (16-byte aligned x and out required)");
     return SA_ERR_ARG;
   }
@@ -262,22 +197,10 @@ extern "C" int sa_dp_perturb_f32(const float* x, uint64_t n, const sa_dp* dp, fl
   if (n == 0) return SA_OK;
   DpArgs a{x,  out, n, dp->sumsq, dp->sumsq_layer, dp->l2_norm_clip, dp->noise_std, dp->num_updates,
            exact_recip_pow2(dp->num_updates), dp->key, dp->counter0 / 4};
-#ifndef SA_DP_GRID_MULT
-#define SA_DP_GRID_MULT 1
-#endif
   int grid;
-  if (kDpTile > 0) {
-    const uint64_t want = ((n + 3) / 4 + 256 * kDpTile - 1) / (256 * kDpTile);
-    if (want > 0x7fffffffull) {
-      sa_set_error("sa_dp_perturb_f32: n too large for the tile grid");
-      return SA_ERR_ARG;
-    }
-    grid = (int)want;
-  } else {
-    const int maxb = occupancy_blocks((const void*)&k_dp_perturb) * SA_DP_GRID_MULT;
-    if (maxb <= 0) return SA_ERR_HIP;
-    const uint64_t want = ((n + 3) / 4 + 255) / 256;
-    grid = (int)(want < (uint64_t)maxb ? want : (uint64_t)maxb);
+  if (!tile_blocks(((n + 3) / 4 + kDpTile - 1) / kDpTile, &grid)) {
+    sa_set_error("sa_dp_perturb_f32: n too large for the tile grid");
+    return SA_ERR_ARG;
   }
   hipLaunchKernelGGL(k_dp_perturb, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   SA_HIP_CHECK(hipGetLastError());

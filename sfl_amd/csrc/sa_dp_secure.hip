@@ -7,14 +7,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sfl_sa.h"
+#include "sa_elems.h"
 #include "sa_internal.h"
-#include "sa_tiles.h"
 #include "sa_philox.h"
 #include "sa_chacha.h"
 
 namespace sa {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using elems::f32x4;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct ChachaKey {
@@ -47,7 +47,7 @@ __device__ __forceinline__ float dp_secure_apply(float x, float scale, double z6
 __global__ void __launch_bounds__(256) k_dp_perturb_secure(const DpSecureArgs a) {
   const uint64_t nb = (a.n + 3) / 4;
   const uint64_t full = a.n / 4;  // blocks with 4 elements
-  const uint64_t b = (uint64_t)stream_tile() * 256 + threadIdx.x;
+  const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= nb) return;
   const float scale = dp_scale(a.sumsq, a.sumsq_layer, a.clip);
   const f32x4* x4 = reinterpret_cast<const f32x4*>(a.x);
@@ -95,13 +95,9 @@ __global__ void __launch_bounds__(256) k_hb_normals(const uint32_t* __restrict__
 }
 
 static bool tile_grid(uint64_t items, const char* who, int* grid) {
-  const uint64_t want = (items + 255) / 256;
-  if (want > 0x7fffffffull) {
-    sa_set_error("%s: too many elements for the tile grid", who);
-    return false;
-  }
-  *grid = (int)want;
-  return true;
+  if (tile_blocks(items, grid)) return true;
+  sa_set_error("%s: too many elements for the tile grid", who);
+  return false;
 }
 
 }  // namespace sa
@@ -110,11 +106,11 @@ using namespace sa;
 
 extern "C" int sa_dp_perturb_secure_f32(const float* x, uint64_t n, const sa_dp_secure* dp, float* out,
                                         void* stream) {
-  if ((n > 0 && (!x || !out)) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) {
+  if ((n > 0 && (!x || !out)) || !aligned16(x) || !aligned16(out)) {
     sa_set_error("sa_dp_perturb_secure_f32: bad arguments (16-byte aligned x and out required)");
     return SA_ERR_ARG;
   }
-  if (!dp || !dp->sumsq || !(dp->num_updates > 0.0f) || (dp->counter0 & 3)) {
+  if (!dp_fields_ok(dp)) {
     sa_set_error("sa_dp_perturb_secure_f32: bad sa_dp_secure (sumsq set, num_updates > 0, counter0 %% 4 == 0 "
                  "required)");
     return SA_ERR_ARG;
@@ -132,7 +128,7 @@ extern "C" int sa_dp_perturb_secure_f32(const float* x, uint64_t n, const sa_dp_
 
 extern "C" int sa_chacha20_keystream(const uint32_t key[8], uint64_t nonce, uint64_t block0, uint64_t n_blocks,
                                      uint32_t* out, void* stream) {
-  if (!key || (n_blocks > 0 && !out) || ((uintptr_t)out & 15)) {
+  if (!key || (n_blocks > 0 && !out) || !aligned16(out)) {
     sa_set_error("sa_chacha20_keystream: bad arguments (key and a 16-byte aligned out required)");
     return SA_ERR_ARG;
   }

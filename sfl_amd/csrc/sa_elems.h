@@ -1,6 +1,7 @@
 // sa_elems.h — a lane's four consecutive elements of a tile, for streaming
 // kernels (sa_stc.hip, sa_scr.hip, sa_coo.hip; sa_quant.hip takes the vector
-// types; all through sa_compress.h): 16-byte loads and stores where the
+// types; all through sa_compress.h; sa_dp.hip, sa_dp_secure.hip and
+// sa_server.hip take the vector types too): 16-byte loads and stores where the
 // caller found every vector 16-byte aligned, element accesses with the same
 // lane-to-element map otherwise.
 #pragma once

@@ -41,6 +41,20 @@ int occupancy_blocks(const void* kernel);  // active 256-thread blocks of `kerne
 int masking_grid_cap(const void* kernel);  // occupancy less sa_set_masking_reserve's CUs
 int check_type(int t, const char* what);   // SA_OK, or SA_ERR_ARG with "<what>: unknown element type" set
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// Grid of a one-pass tile kernel (no grid stride): the blocks of 256 lanes
+// covering `items` lanes; false when a grid's 2^31 - 1 blocks do not (the
+// entry then sets its own message).
+inline bool tile_blocks(uint64_t items, int* grid) {
+  const uint64_t want = (items + 255) / 256;
+  if (want > 0x7fffffffull) return false;
+  *grid = (int)want;
+  return true;
+}
+// what sa_dp and sa_dp_secure (D) both require: sumsq set, num_updates > 0, counter0 % 4 == 0
+template <class D>
+inline bool dp_fields_ok(const D* dp) {
+  return dp && dp->sumsq && dp->num_updates > 0.0f && !(dp->counter0 & 3);
+}
 
 constexpr int kSumMaxIn = 32;    // inputs per launch of the server sums (sa_server.hip)
 constexpr int kMaxLocal = 8;     // co-located clients per fused launch

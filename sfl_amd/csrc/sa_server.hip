@@ -5,8 +5,8 @@
 #include <string.h>
 
 #include "../../include/sfl_sa.h"
+#include "sa_elems.h"
 #include "sa_internal.h"
-#include "sa_tiles.h"
 
 namespace sa {
 
@@ -24,7 +24,7 @@ constexpr int kUnroll = 4;
 constexpr int kTileAccesses = 256 * kUnroll;  // 16-B accesses per block and input
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
+using elems::f64x2;
 
 template <typename T>
 __device__ __forceinline__ T ld_nt(const T* p) {
@@ -55,7 +55,7 @@ template <typename V>
 __global__ void __launch_bounds__(256) k_sum(const SumArgs<V> a) {
   static_assert(sizeof(V) == 16 && sizeof(typename SumArgs<V>::T) == 8, "two 8-B elements per access");
   const uint64_t n2 = a.n / 2;
-  const uint64_t base = (uint64_t)stream_tile() * kTileAccesses + threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * kTileAccesses + threadIdx.x;
   const int j0 = a.accumulate ? 0 : 1;
   const V* first = reinterpret_cast<const V*>(a.accumulate ? a.out : a.in[0]);
   V s[kUnroll];
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256) k_decode(const uint64_t* __restrict__ s, 
                                                 double div, const double* __restrict__ divv,
                                                 double* __restrict__ out) {
   const uint64_t n2 = n / 2;
-  const uint64_t base = (uint64_t)stream_tile() * kTileAccesses + threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * kTileAccesses + threadIdx.x;
   const u64x2* s2 = reinterpret_cast<const u64x2*>(s);
   const f64x2* d2 = reinterpret_cast<const f64x2*>(divv);
   f64x2* o2 = reinterpret_cast<f64x2*>(out);
@@ -133,12 +133,12 @@ __global__ void __launch_bounds__(256) k_decode_unaligned(const uint64_t* __rest
 // one block per tile of kTileAccesses 16-B accesses (at least one block for
 // the odd-element lane)
 static int tile_grid(uint64_t n) {
-  const uint64_t b = (n / 2 + kTileAccesses - 1) / kTileAccesses;
-  if (b >= (1ull << 31)) {
+  int grid;
+  if (!tile_blocks((n / 2 + kUnroll - 1) / kUnroll, &grid)) {  // a lane's kUnroll accesses
     sa_set_error("vector of %llu elements exceeds one server-kernel launch", (unsigned long long)n);
     return -1;
   }
-  return b < 1 ? 1 : (int)b;
+  return grid < 1 ? 1 : grid;
 }
 
 static int stream_grid(uint64_t work_items, const void* kfn) {

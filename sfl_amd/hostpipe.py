@@ -76,8 +76,9 @@ def pcopy(dst: np.ndarray, src: np.ndarray) -> None:
     list(_pool().map(lambda a: np.copyto(dst[a:a + step], src[a:a + step]), range(0, dst.size, step)))
 
 
-# chunks per pipelined call (SFL_HOSTPIPE_CHUNKS; a party's mask_payload asks for 16 itself)
-CHUNKS = int(os.environ.get("SFL_HOSTPIPE_CHUNKS", "8"))
+# chunks per pipelined call (a party's mask_payload asks for 16 itself); 16 here
+# changed nothing measurable (profiles/r06/chunks_ab.jsonl)
+CHUNKS = 8
 
 
 def chunk_bounds(n: int, target: int | None = None, lo_elems: int = 1 << 20, hi_elems: int = 1 << 24,
@@ -428,11 +429,11 @@ class Issued:
     for, with chunk j+1's behind them.  Not all at once: a stream holds a
     bounded number of outstanding copies, and issuing config 5's 512 copies
     up front blocked the caller until most had finished, so no launch
-    overlapped them.  With a lazily registering ``pin``, each piece is
-    registered just before its copy is issued (``Pinned.split``), so the
-    registration of chunk j+1 runs while chunk j's DMA is in flight."""
-
-    LOOKAHEAD = int(os.environ.get("SFL_HOSTPIPE_LOOKAHEAD", "1"))  # chunks issued ahead of the one asked for
+    overlapped them; two chunks ahead instead of one was no faster (633-650
+    against 624-635 ms per call, profiles/r06/README.md).  With a lazily
+    registering ``pin``, each piece is registered just before its copy is
+    issued (``Pinned.split``), so the registration of chunk j+1 runs while
+    chunk j's DMA is in flight."""
 
     def __init__(self, stream, chunks, pin=None):
         self.stream, self.chunks = stream, chunks
@@ -462,7 +463,7 @@ class Issued:
             self.events.append(e)
 
     def ready(self, j: int):
-        while len(self.events) <= min(j + self.LOOKAHEAD, len(self.chunks) - 1):
+        while len(self.events) <= min(j + 1, len(self.chunks) - 1):
             self._issue(len(self.events))
         return self.events[j]
 
@@ -480,16 +481,10 @@ def _tensor(a: np.ndarray):
         return torch.from_numpy(a)
 
 
-# SFL_HOSTPIPE_REGISTER=0: never register the caller's inputs (the feeder
-# stages every one that is not a pooled result)
-REGISTER = os.environ.get("SFL_HOSTPIPE_REGISTER", "1") != "0"
-# SFL_HOSTPIPE_LAZY_REGISTER=0: register every large input whole on entry
-# instead of piece by piece as its copies are issued
-LAZY_REGISTER = os.environ.get("SFL_HOSTPIPE_LAZY_REGISTER", "1") != "0"
 LAZY_MIN_BYTES = 64 << 20  # smaller arrays are registered whole on entry
 # each lazy registration covers at least LAZY_GROWTH x what the array has
 # registered so far (1: exactly what the copy at hand needs)
-LAZY_GROWTH = int(os.environ.get("SFL_HOSTPIPE_LAZY_GROWTH", "2"))
+LAZY_GROWTH = 2
 
 
 class _Span:
@@ -521,20 +516,20 @@ class Pinned:
     registered memory): nothing stays registered and the caller stages
     through the feeder.  Unregistered on exit.
 
-    Lazily (``LAZY_REGISTER``, arrays of ``LAZY_MIN_BYTES`` or more):
-    nothing is registered on entry; ``split`` registers an array's pages as
-    ``Issued`` reaches them, each time at least ``LAZY_GROWTH`` x what it
-    holds already (chunk 0, then 1, then 2-3, 4-7, ...: few calls, ~0.1-0.2
-    ms each whatever their size), so registering 32 GB of config-5 inputs
-    (57 ms before the first copy) overlaps the copies of earlier chunks.  A
+    Arrays of ``LAZY_MIN_BYTES`` or more are registered lazily: nothing
+    on entry; ``split`` registers an array's pages as ``Issued`` reaches
+    them, each time at least ``LAZY_GROWTH`` x what it holds already (chunk
+    0, then 1, then 2-3, 4-7, ...: few calls, ~0.1-0.2 ms each whatever
+    their size), so registering 32 GB of config-5 inputs (57 ms before the
+    first copy) overlaps the copies of earlier chunks (whole on entry:
+    664-670 against 636-638 ms, profiles/r06/lazy_register_ab.jsonl).  A
     copy never spans two registrations: ``split`` cuts it at their joins.
     A registration the driver refuses leaves the rest of that array to be
     staged piece by piece (``Issued``)."""
 
-    def __init__(self, arrays, register: bool = True, lazy: bool | None = None):
+    def __init__(self, arrays, register: bool = True):
         self.arrays = [a for a in arrays if a.nbytes]
-        self.register = register and REGISTER
-        self.lazy = LAZY_REGISTER if lazy is None else lazy
+        self.register = register
         self.done = []  # start addresses of our registrations
         self.spans: list[_Span] = []
         self._keys = []
@@ -561,7 +556,7 @@ class Pinned:
                 self.__exit__(None, None, None)
                 return self
             p0, p1 = a.ctypes.data, a.ctypes.data + a.nbytes
-            if self.lazy and a.nbytes >= LAZY_MIN_BYTES:
+            if a.nbytes >= LAZY_MIN_BYTES:
                 self.spans.append(_Span(p0, p1))
             elif not self._reg(p0, p1):
                 self.__exit__(None, None, None)

@@ -390,18 +390,32 @@ def sum_f64(ins: Sequence[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 # GaussianModelDP pre-step (sa_sumsq_f32 / sa_dp_perturb_f32 / sa_mask_dp)
 # ---------------------------------------------------------------------------
-def make_dp(sumsq: torch.Tensor, *, l2_norm_clip: float, noise_std: float, num_updates: float, key: int,
-            counter0: int = 0, sumsq_layer: torch.Tensor | None = None) -> L.DP:
+_M64 = (1 << 64) - 1
+
+
+def _fill_dp(d, sumsq, sumsq_layer, l2_norm_clip, noise_std, num_updates, counter0):
+    """The fields sa_dp and sa_dp_secure share."""
     if counter0 % 4:
         raise ValueError("counter0 must be a multiple of 4")
-    d = L.DP()
     d.sumsq = sumsq.data_ptr()
     d.sumsq_layer = sumsq_layer.data_ptr() if sumsq_layer is not None else None
     d.l2_norm_clip = float(l2_norm_clip)
     d.noise_std = float(noise_std)
     d.num_updates = float(num_updates)
-    d.key = int(key) & ((1 << 64) - 1)
     d.counter0 = int(counter0)
+    return d
+
+
+def _dp_operands(who: str, x: torch.Tensor, out: torch.Tensor) -> None:
+    _require_gpu(x, out)
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() != x.numel():
+        raise ValueError(f"{who}: float32 x and out of equal size")
+
+
+def make_dp(sumsq: torch.Tensor, *, l2_norm_clip: float, noise_std: float, num_updates: float, key: int,
+            counter0: int = 0, sumsq_layer: torch.Tensor | None = None) -> L.DP:
+    d = _fill_dp(L.DP(), sumsq, sumsq_layer, l2_norm_clip, noise_std, num_updates, counter0)
+    d.key = int(key) & _M64
     return d
 
 
@@ -417,9 +431,7 @@ def sumsq_f32(x: torch.Tensor, out: torch.Tensor, partials: torch.Tensor, *, acc
 
 
 def dp_perturb(x: torch.Tensor, out: torch.Tensor, dp: L.DP) -> torch.Tensor:
-    _require_gpu(x, out)
-    if x.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() != x.numel():
-        raise ValueError("dp_perturb: float32 x and out of equal size")
+    _dp_operands("dp_perturb", x, out)
     L.check(L.lib().sa_dp_perturb_f32(_ptr(x), x.numel(), C.byref(dp), _ptr(out), C.c_void_p(_stream(out))),
             "sa_dp_perturb_f32")
     return out
@@ -444,29 +456,16 @@ def mask_dp(x: torch.Tensor, out: torch.Tensor, streams: Sequence[tuple], dp: L.
 # halves it is made of: sa_chacha20_keystream, sa_hb_normals_f64).  uint32
 # words are carried as ``torch.int32`` tensors (same bits).
 # ---------------------------------------------------------------------------
-_M64 = (1 << 64) - 1
-
-
 def make_dp_secure(sumsq: torch.Tensor, *, l2_norm_clip: float, noise_std: float, num_updates: float, key: bytes,
                    nonce: int, counter0: int = 0, sumsq_layer: torch.Tensor | None = None) -> L.DPSecure:
-    if counter0 % 4:
-        raise ValueError("counter0 must be a multiple of 4")
-    d = L.DPSecure()
-    d.sumsq = sumsq.data_ptr()
-    d.sumsq_layer = sumsq_layer.data_ptr() if sumsq_layer is not None else None
-    d.l2_norm_clip = float(l2_norm_clip)
-    d.noise_std = float(noise_std)
-    d.num_updates = float(num_updates)
+    d = _fill_dp(L.DPSecure(), sumsq, sumsq_layer, l2_norm_clip, noise_std, num_updates, counter0)
     d.key = L.chacha_key_words(key)
     d.nonce = int(nonce) & _M64
-    d.counter0 = int(counter0)
     return d
 
 
 def dp_perturb_secure(x: torch.Tensor, out: torch.Tensor, dp: L.DPSecure) -> torch.Tensor:
-    _require_gpu(x, out)
-    if x.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() != x.numel():
-        raise ValueError("dp_perturb_secure: float32 x and out of equal size")
+    _dp_operands("dp_perturb_secure", x, out)
     L.check(L.lib().sa_dp_perturb_secure_f32(_ptr(x), x.numel(), C.byref(dp), _ptr(out), C.c_void_p(_stream(out))),
             "sa_dp_perturb_secure_f32")
     return out

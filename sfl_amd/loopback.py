@@ -23,11 +23,12 @@ The GPU kernels are the product path; nothing here falls back to the CPU.
 Host buffers that leave through a socket (every client's masked vector, the
 server's float64 result) are ``SharedHostBuffer``s: memfd-backed pages that
 are HIP-registered, so the D2H copy lands in them directly.  They are sent
-with ``sendall`` (a copy into the kernel); ``SFL_LOOPBACK_SEND=sendfile``
-hands the page references to the socket instead -- no send-side copy, but
-measured no faster at 8 x 100M and slower at 32 x 256M (DESIGN.md §7,
+with ``sendall`` (a copy into the kernel): ``sendfile`` from the memfd pages
+has no send-side copy, but measured no faster at 8 x 100M and 26 % slower at
+32 x 256M (DESIGN.md §7, profiles/r03/loopback_*_ab.jsonl;
 tools/socket_floor.py for the transport alone).  Clients receive the result
-while they send, and GPU waits poll instead of spinning a core.
+while they send (``LoopbackClient.submit`` says why), and GPU waits poll
+instead of spinning a core.
 """
 
 from __future__ import annotations
@@ -77,26 +78,12 @@ class StageClock:
             return {k: {"wall_s": v[0], "cpu_s": v[1], "calls": v[2]} for k, v in sorted(self._t.items())}
 
 
-# Knobs for same-box A/B measurements of the host path (tools/loopback_bench.py
-# --ab); the defaults are the product's choices.
-#   SFL_LOOPBACK_SEND=copy|sendfile   sendall() (a copy into the kernel), or sendfile() from the memfd pages
-#                                     (no send-side copy, but page-granular kernel work: measured no faster
-#                                     at 8 x 100M and 26 % slower at 32 x 256M, profiles/r03/loopback_*_ab.jsonl)
-#   SFL_LOOPBACK_WAIT=poll|spin       wait for a GPU event by polling with short sleeps, or in hipEventSynchronize
-#   SFL_LOOPBACK_CLIENT_RX=concurrent|after   a client reads the result while it sends, or after (round 2;
-#                                     with SEND=sendfile that can stall on the box's kernel: copy only)
-def _send_mode() -> str:
-    return os.environ.get("SFL_LOOPBACK_SEND", "copy")
-
-
 def wait_event(e) -> None:
     """Wait for a recorded GPU event.  hipEventSynchronize spins a CPU core
     for the whole wait; the loopback party runs ~20 threads per process
     against the box's CPU share, so a wait polls with ~50 us sleeps instead
-    and leaves the core to the socket copies."""
-    if os.environ.get("SFL_LOOPBACK_WAIT", "poll") == "spin":
-        e.synchronize()
-        return
+    and leaves the core to the socket copies (5.34 against 4.92 s per round
+    at 32 x 256M, HISTORY.md's interleaved A/B)."""
     while not e.query():
         time.sleep(50e-6)
 
@@ -116,12 +103,8 @@ def _hip():
 class SharedHostBuffer:
     """``nbytes`` of memfd-backed host memory, mapped, faulted in and
     HIP-registered (hipHostRegister): device copies land in it directly (torch
-    sees it as pinned), and ``send(sock, lo, hi)`` ships a byte range --
-    with ``sendall``, or with ``os.sendfile`` (page references handed to the
-    socket, no send-side copy) under SFL_LOOPBACK_SEND=sendfile.  With
-    sendfile the pages must not change until the peer has read them; the
-    round protocol guarantees that (a party writes a buffer again only after
-    every peer answered the frame that carried it)."""
+    sees it as pinned), and ``send(sock, lo, hi)`` ships a byte range with
+    ``sendall``."""
 
     def __init__(self, nbytes: int, dtype=np.float64):
         import ctypes
@@ -150,21 +133,9 @@ class SharedHostBuffer:
         return torch.from_numpy(self.array)
 
     def send(self, sock: socket.socket, lo: int, hi: int) -> None:
-        """Send bytes [lo, hi) of the buffer (socket.sendfile: os.sendfile
-        plus the wait for a full socket buffer that a socket with a timeout,
-        i.e. a non-blocking descriptor, needs)."""
-        if hi <= lo:
-            return
-        if _send_mode() == "copy":
+        """Send bytes [lo, hi) of the buffer."""
+        if hi > lo:
             sock.sendall(memoryview(self.array).cast("B")[lo:hi])
-            return
-        f = open(self.fd, "rb", buffering=0, closefd=False)  # a file object on the memfd (no new open)
-        try:
-            sent = sock.sendfile(f, lo, hi - lo)
-        finally:
-            f.close()
-        if sent != hi - lo:
-            raise W.WireError(f"sendfile sent {sent} of {hi - lo} bytes (peer closed?)")
 
     def _close_map(self):
         self.array = None
@@ -747,14 +718,9 @@ def client_process(parties: list, port: int, n: int, rounds: int, gpu: int, fxp_
             ce = max(1, min(n, chunk_elems()))
             res = np.empty(n, dtype=np.float64) if keep_results else [np.empty(ce, dtype=np.float64)
                                                                        for _ in range(2)]
-            after = os.environ.get("SFL_LOOPBACK_CLIENT_RX", "concurrent") == "after"
             for r in range(rounds):
-                if after:  # A/B only (round 2's client): read the result once everything is sent
-                    st = cl.submit(xs[r], r, weight)
-                    cl.result(n, into=res)
-                else:
-                    st = cl.submit(xs[r], r, weight, result_into=res)
-                    cl.result(n)
+                st = cl.submit(xs[r], r, weight, result_into=res)
+                cl.result(n)
                 st["result_xor"] = cl.last_result_xor
                 st["stages"]["client: result recv thread (socket -> numpy, from the start of submit)"] = dict(
                     cl.last_result_recv, calls=1)

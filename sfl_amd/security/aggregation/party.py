@@ -28,7 +28,6 @@ spawned process per party.
 
 from __future__ import annotations
 
-import os
 import threading
 from dataclasses import dataclass, field
 
@@ -37,12 +36,6 @@ import numpy as np
 from .masker import Masker
 from .payload import (SMALL_CALL_BYTES, element_types, flat_host, host_weight, is_torch, np_dtype, scalar_weight,
                       shape, split_layers, to_device, torch_dtypes)
-
-# the server's large sum_decode stages vectors that are not pooled results
-# (vectors deserialised from other processes) through the feeder; with
-# SFL_SERVER_REGISTER=1 it registers them lazily instead: 125-129 against
-# 121-123 ms at 8 x 100M (tools/archive/server_register_ab.sh)
-SERVER_REGISTER = os.environ.get("SFL_SERVER_REGISTER", "0") == "1"
 
 
 @dataclass
@@ -474,8 +467,9 @@ def _sum_decode_pipelined(u64s, digests, fxp_bits, divisor, dev):
 
     # vectors received from parties in this process sit in pooled (registered)
     # results: copied async as they are; anything else (vectors deserialised
-    # from another process) is staged by the feeder (or, SERVER_REGISTER,
-    # registered lazily as its copies are reached)
-    out, got = H.run_chunks("sum_decode", dev, bounds, ins, np.float64, setup, register=SERVER_REGISTER)
+    # from another process) is staged by the feeder: registering it lazily
+    # instead took 125-129 against 121-123 ms at 8 x 100M
+    # (tools/archive/server_register_ab.sh)
+    out, got = H.run_chunks("sum_decode", dev, bounds, ins, np.float64, setup, register=False)
     _check_digests(got.view(np.uint64).tolist(), digests)
     return out

@@ -97,9 +97,8 @@ def test_loopback_client_reproduces_numpy_rejection():
             assert np.array_equal(masked[r][c], m[c]), (r, c)
 
 
-@pytest.mark.parametrize("send", ["copy", "sendfile"])
-def test_loopback_chunks_without_result_copies(monkeypatch, send):
-    """Both send modes over many chunks (masked vectors D2H into registered
+def test_loopback_chunks_without_result_copies(monkeypatch):
+    """Many chunks (masked vectors D2H into registered
     memfd pages chunk by chunk, each sent as it lands; the result D2H'd into
     the server's pages and broadcast from them), with no copy of the result
     kept by the server or the clients (keep_results=False: the clients
@@ -110,8 +109,7 @@ def test_loopback_chunks_without_result_copies(monkeypatch, send):
         pytest.skip("no GPU")
     from sfl_amd.loopback import run_loopback, synthetic_gradient
 
-    monkeypatch.setenv("SFL_LOOPBACK_SEND", send)  # the spawned clients inherit both
-    monkeypatch.setenv("SFL_LOOPBACK_CHUNK_ELEMS", "8192")  # 9 chunks
+    monkeypatch.setenv("SFL_LOOPBACK_CHUNK_ELEMS", "8192")  # 9 chunks (the spawned clients inherit it)
     names = ["p0", "p1", "p2", "p3"]
     n, rounds = 70_001, 3
     seeds = o.seeds_for(names)

@@ -278,7 +278,7 @@ def test_in_process_large_general_payloads(kind, C, monkeypatch):
 class _NotPinned:
     """H.Pinned stand-in whose registration is refused: the feeder path."""
 
-    def __init__(self, arrays, register=True, lazy=None):
+    def __init__(self, arrays, register=True):
         self.ok = False
         self.spans, self.stats = [], {}
 
@@ -420,12 +420,10 @@ def test_lazy_registration_bit_exact(growth, refuse_after, monkeypatch):
     got = P.sum_decode(*wires, weights=[0.75] * 3, average=True, gpu=0)
     assert np.array_equal(np.concatenate([np.asarray(g).reshape(-1) for g in got]), want)
     # vectors as another process would hand them over: fresh arrays, not
-    # pooled results -- registered lazily by the server, or staged
-    for server_register in (True, False):
-        monkeypatch.setattr(P, "SERVER_REGISTER", server_register)
-        fresh = [dataclasses.replace(w, u64=w.u64.copy()) for w in wires]
-        got = P.sum_decode(*fresh, weights=[0.75] * 3, average=True, gpu=0)
-        assert np.array_equal(np.concatenate([np.asarray(g).reshape(-1) for g in got]), want), server_register
+    # pooled results -- staged by the server's feeder
+    fresh = [dataclasses.replace(w, u64=w.u64.copy()) for w in wires]
+    got = P.sum_decode(*fresh, weights=[0.75] * 3, average=True, gpu=0)
+    assert np.array_equal(np.concatenate([np.asarray(g).reshape(-1) for g in got]), want)
     pair = {(a, b): seeds[a][b] for a in NAMES for b in NAMES if a != b}
     pyus = [PYU(nm, 0) for nm in NAMES]
     agg = SecureAggregator(PYU("server", 0), pyus, seeds=pair)

@@ -192,7 +192,7 @@ def test_lazy_pinned_registers_chunk_by_chunk(monkeypatch):
     ll = _parties(2, n)
     bounds = H.page_bounds(H.chunk_bounds(n), ll)
     arrays = [a for p in ll for a in p]
-    with H.Pinned(arrays, lazy=True) as pin:
+    with H.Pinned(arrays) as pin:
         assert pin.ok and fake.ranges == []  # nothing registered on entry
         got = _split_all(pin, ll[0], bounds)
         # joins on pages: every piece is one registered range
@@ -218,7 +218,7 @@ def test_lazy_pinned_grows_geometrically(monkeypatch):
     ll = _parties(1, n)
     bounds = H.page_bounds(H.chunk_bounds(n, target=16), ll)
     assert len(bounds) == 16
-    with H.Pinned(ll[0], lazy=True) as pin:
+    with H.Pinned(ll[0]) as pin:
         got = _split_all(pin, ll[0], bounds)
         assert len(fake.ranges) == 5
         assert all(reg for _, r in got for _, _, reg in r)
@@ -237,7 +237,7 @@ def test_lazy_pinned_cuts_copies_at_registration_joins(monkeypatch):
     n = 20_000_003
     ll = [_parties(1, n, np.float64)[0]]
     bounds = H.chunk_bounds(n)  # joins off the pages: pieces straddle a join
-    with H.Pinned(ll[0], lazy=True) as pin:
+    with H.Pinned(ll[0]) as pin:
         got = _split_all(pin, ll[0], bounds)
         joins = {r0 for r0, _ in fake.ranges[1:]}
         for a, r in got:
@@ -256,7 +256,7 @@ def test_lazy_pinned_refused_mid_call_stages_the_rest(monkeypatch):
     n = 40_000_000
     ll = _parties(1, n)
     bounds = H.page_bounds(H.chunk_bounds(n), ll)
-    with H.Pinned(ll[0], lazy=True) as pin:
+    with H.Pinned(ll[0]) as pin:
         got = _split_all(pin, ll[0], bounds)
         regs = [all(reg for _, _, reg in r) for _, r in got]
         assert regs[:3] == [True] * 3 and not any(regs[3:])
@@ -266,5 +266,5 @@ def test_lazy_pinned_refused_mid_call_stages_the_rest(monkeypatch):
     # registered, the caller stages (Feeder)
     fake = _RangeHip(allow=0)
     monkeypatch.setattr(H, "_hip", lambda: fake)
-    with H.Pinned([np.ones(1 << 20, np.float32)], lazy=True) as pin:
+    with H.Pinned([np.ones(1 << 20, np.float32)]) as pin:
         assert not pin.ok

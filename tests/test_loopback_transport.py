@@ -1,6 +1,5 @@
 """The loopback runtime's send path (sfl_amd.loopback.SharedHostBuffer) on
-the CPU, in both modes (sendall, and socket.sendfile of the memfd pages):
-byte ranges sent over a socket with a
+the CPU: byte ranges sent over a socket with a
 timeout (a non-blocking descriptor) whose buffer fills while the receiver
 sleeps -- every byte arrives, in order, in several ranges.  (HIP registration
 of the pages is exercised on the GPU by tests/test_gpu_loopback.py.)"""
@@ -27,9 +26,7 @@ class _Unregistered(lb.SharedHostBuffer):
         self._registered = False
 
 
-@pytest.mark.parametrize("send", ["copy", "sendfile"])
-def test_send_ranges_through_a_full_socket_buffer(monkeypatch, send):
-    monkeypatch.setenv("SFL_LOOPBACK_SEND", send)
+def test_send_ranges_through_a_full_socket_buffer():
     n = 96 << 20
     buf = _Unregistered(n)
     srv = socket.create_server(("127.0.0.1", 0))
