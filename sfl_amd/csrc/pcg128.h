@@ -71,5 +71,44 @@ SA_HD constexpr u128 inv128(u128 a) {
 
 constexpr int kBlockThreads = 256;  // masking-kernel workgroup
 constexpr int kDpBlock = 4;         // elements per Philox counter block (DP noise)
+constexpr int kE = 2;                      // masking kernel: elements per lane per tile
+constexpr int kTile = kBlockThreads * kE;  // elements per workgroup tile (512)
+
+// The masking kernel's draw (sa_draw3.h, SA_PCG_DRAW_ASM) forms the weight-2^32
+// column of S * M + C as O1 = s0*a1 + c1 + s1*a0 in ONE 64-bit register pair
+// and drops the carry out of it.  With 32-bit limbs and c1 < 2^32,
+// O1 <= (2^32 - 1)(a0 + a1 + 1), below 2^64 exactly when a0 + a1 + 1 <= 2^32
+// (a0, a1: the multiplier's two low limbs; tight -- at 2^32 + 2 the all-ones
+// state overflows).  The draw is correct only for such a multiplier.
+SA_HD constexpr bool carry_free(u128 mult) {
+  return (uint64_t)(uint32_t)mult + (uint64_t)(uint32_t)(mult >> 32) + 1 <= ((uint64_t)1 << 32);
+}
+static_assert(carry_free(kPcgMult), "PCG64's multiplier: the plain step's three-carry draw");
+
+// The masking launch's grid.  A tile's first element is reached by the merged
+// tile jump A^J, J = grid * kTile - (kE - 1) draws, so the grid decides whether
+// that multiplier is carry-free.  Among 1..cap: the smallest grid >=
+// min(tiles, cap) whose jump qualifies (a block without a tile runs no
+// iteration, so a few idle blocks are free); if there is none up to cap, the
+// largest qualifying grid below; 0 if none at all.  (Of the grids 1..2048,
+// 1,048 qualify and no run of non-qualifying ones is longer than 8.)
+SA_HD constexpr bool grid_carry_free(uint64_t grid) {
+  return carry_free(jump_of(grid * kTile - (kE - 1)).mult);
+}
+SA_HD constexpr int qualifying_grid(uint64_t tiles, int cap) {
+  if (cap < 1) return 0;
+  const int want = tiles < (uint64_t)cap ? (tiles < 1 ? 1 : (int)tiles) : cap;
+  for (int g = want; g <= cap; g++)
+    if (grid_carry_free((uint64_t)g)) return g;
+  for (int g = want - 1; g >= 1; g--)
+    if (grid_carry_free((uint64_t)g)) return g;
+  return 0;
+}
+static_assert(qualifying_grid(1, 512) == 2 && qualifying_grid(6, 512) == 8 && qualifying_grid(7, 512) == 8 &&
+                  qualifying_grid(9, 512) == 11 && qualifying_grid(16, 512) == 20 &&
+                  qualifying_grid(64, 512) == 64 && qualifying_grid(512, 512) == 512 &&
+                  qualifying_grid(1000000, 512) == 512 && qualifying_grid(1000000, 511) == 508 &&
+                  qualifying_grid(1000000, 496) == 495 && qualifying_grid(1000000, 256) == 255,
+              "grid choices, checked against pow(A, g * 512 - 1, 2^128)");
 
 }  // namespace sa

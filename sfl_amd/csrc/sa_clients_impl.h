@@ -14,7 +14,7 @@
 //
 // Loop order inside a tile is stream-outer: streams are taken in groups of
 // two (Sched: two streams whose accumulators are disjoint, drawn by one
-// interleaved asm block from sa_draw2.h) and the lane draws both of its
+// interleaved asm block from sa_draw3.h) and the lane draws both of its
 // elements for a group back to back, so a group's constants (inc, inc*G_J,
 // sign mask) serve two draws per stream.  They are scalar-loaded from the
 // kernarg segment into SGPRs, laid out by group (sa_internal.h, GroupArg):
@@ -46,7 +46,7 @@
 
 #include "../../include/sfl_sa.h"
 #include "pcg128.h"
-#include "sa_draw2.h"
+#include "sa_draw3.h"
 #include "sa_internal.h"
 #include "sa_philox.h"
 
@@ -79,8 +79,8 @@ static __device__ uint64_t g_sa_ts[kTsWaves][kTsWords];
 #define SA_TS(v) (void)0
 #endif
 
-constexpr int kE = 2;                       // elements per lane per tile
-constexpr int kTile = kBlockThreads * kE;   // elements per workgroup tile (512)
+// kE (elements per lane per tile) and kTile (elements per workgroup tile, 512)
+// come from pcg128.h, where the grid choice (qualifying_grid) needs them.
 
 struct PowTable {
   Jump e[64];
@@ -289,41 +289,50 @@ __device__ __forceinline__ uint32_t vreg(uint32_t x) {
 //   s1a1 + s2a0 + C23) on v_mad_u64_u32 -- the increment's two low words enter
 //   as separate zero-extended addends so the first two mads cannot carry --
 //   the four limb-3 products summed by one v_mul_lo_u32 and three
-//   v_mad_u64_u32 (only the low word is kept), joined by carry adds whose
-//   carry-ins are the mads' own carry-outs -- 9 mads + 1 mul_lo + 4 adds +
-//   1 mov (the paired draws of sa_draw2.h, which do nearly all the work,
-//   keep limbs 0-1 in one VGPR pair written in place and need no mov).
+//   v_mad_u64_u32 (only the low word is kept), joined by three carry adds
+//   (r1 = E0.hi + O1.lo; r2 = E2.lo + O1.hi + cy; r3 = E2.hi + L3 + cy) --
+//   9 mads + 1 mul_lo + 3 adds + 1 mov (the paired draws of sa_draw3.h, which
+//   do nearly all the work, keep limbs 0-1 in one VGPR pair written in place
+//   and need no mov).
+//   PRECONDITION: the middle column O1 = s0a1 + c1 + s1a0 must stay below
+//   2^64, i.e. the multiplier's low limbs satisfy a0 + a1 + 1 <= 2^32
+//   (pcg128.h, carry_free) -- then its second mad's carry-out is always 0 and
+//   is discarded.  PCG64's multiplier qualifies (static_assert there); the
+//   tile jump's A^J does for the grids launch_clients picks, which checks it
+//   on the host for every launch.  (sa_draw2.h keeps the four-carry form for
+//   any multiplier.)
 //   Then x = hi^lo^m (two v_bitop3) and t = rotr(x, hi>>58) as two 64-bit
 //   shifts whose disjoint parts one v_lshl_add_u64 adds: y = x >> r,
 //   z = x << (63 - r), t = (z << 1) + y (r = 0: z << 1 vanishes, t = x); the
 //   raw==0 test (hi == lo <=> x == m:m) as one 64-bit compare whose lane
 //   mask the SALU ORs into `zs` (a per-tile SGPR pair), and the accumulation
-//   (below).  The same form as sa_draw2.h's paired draws (tools/gen_draw2.py).
+//   (below).  The same form as sa_draw3.h's paired draws (tools/gen_draw2.py
+//   --carry3).
 //
-// Carries live in three SGPR pairs, reused as they die (k1: a discarded
-// carry-out; k2: kO, c2, then the acc_v borrow; k3: discarded carry-outs, c1).
-// Every VALU-written SGPR (carries, VCC) is read >= 2 instructions later
-// (gfx950 VALU-SGPR-write -> VALU-read hazard).  v0-v9 are fixed scratch (low
-// registers, so the kernel's VGPR budget is not raised).  Single draws only
-// serve schedules with an odd leftover stream.
+// Carries live in three SGPR pairs, reused as they die (k1: discarded
+// carry-outs, also those of the two mads that sit between the first two joins
+// while k3 holds c1; k2: c2, then the acc_v borrow; k3: discarded carry-outs,
+// c1).  Every VALU-written SGPR (carries, VCC) is read no earlier than the
+// third instruction after its write (gfx950 VALU-SGPR-write -> VALU-read
+// hazard).  v0-v9 are fixed scratch (low registers, so the kernel's VGPR
+// budget is not raised).  Single draws only serve schedules with an odd
+// leftover stream.
 #define SA_PCG_DRAW_ASM                                                                  \
   "v_mad_u64_u32 v[0:1], %[k1], %[s0], %[a0], %[c0]\n\t"    /* E0 = s0a0 + c0 < 2^64 */  \
   "v_mad_u64_u32 v[2:3], %[k3], %[s0], %[a1], %[c1]\n\t"    /* O1 = s0a1 + c1 < 2^64 */  \
   "v_mad_u64_u32 v[4:5], %[k3], %[s0], %[a2], %[c23]\n\t"   /* E2 = s0a2 + C23 */       \
   "v_mul_lo_u32 v6, %[s0], %[a3]\n\t"                       /* L3 = p03 */               \
-  "v_mad_u64_u32 v[2:3], %[k2], %[s1], %[a0], v[2:3]\n\t"   /* O1 += s1a0, kO */        \
+  "v_mad_u64_u32 v[2:3], %[k3], %[s1], %[a0], v[2:3]\n\t"   /* O1 += s1a0, < 2^64 */    \
   "v_mad_u64_u32 v[4:5], %[k3], %[s1], %[a1], v[4:5]\n\t"                                \
   "v_mad_u64_u32 v[6:7], %[k3], %[s1], %[a2], v[6:7]\n\t"   /* L3 += p12 (low word) */  \
   "v_mad_u64_u32 v[4:5], %[k3], %[s2], %[a0], v[4:5]\n\t"                                \
-  "v_mad_u64_u32 v[6:7], %[k3], %[s2], %[a1], v[6:7]\n\t"   /* L3 += p21 */             \
-  "v_mad_u64_u32 v[6:7], %[k3], %[s3], %[a0], v[6:7]\n\t"   /* L3 += p30 */             \
   "v_add_co_u32_e64 %[s1], %[k3], v1, v2\n\t"              /* r1 = e1 + o1, c1 */       \
-  "v_addc_co_u32_e64 %[s3], %[k2], v5, v6, %[k2]\n\t"      /* r3 = e3 + L3 + kO */      \
-  "v_mov_b32_e32 %[s0], v0\n\t"                             /* r0 = e0 */                \
+  "v_mad_u64_u32 v[6:7], %[k1], %[s2], %[a1], v[6:7]\n\t"   /* L3 += p21 (k3 is c1) */  \
+  "v_mad_u64_u32 v[6:7], %[k1], %[s3], %[a0], v[6:7]\n\t"   /* L3 += p30 */             \
   "v_addc_co_u32_e64 %[s2], %[k2], v4, v3, %[k3]\n\t"      /* r2 = e2 + o2 + c1, c2 */  \
+  "v_mov_b32_e32 %[s0], v0\n\t"                             /* r0 = e0 */                \
   "v_bitop3_b32 v0, %[s0], %[s2], %[m] bitop3:0x96\n\t"    /* xl */                     \
-  "s_nop 0\n\t"                                                                          \
-  "v_addc_co_u32_e64 %[s3], %[k3], %[s3], 0, %[k2]\n\t"    /* r3 += c2 */               \
+  "v_addc_co_u32_e64 %[s3], %[k3], v5, v6, %[k2]\n\t"      /* r3 = e3 + L3 + c2 */      \
   "v_bitop3_b32 v1, %[s1], %[s3], %[m] bitop3:0x96\n\t"    /* xh */                     \
   "v_lshrrev_b32_e32 v2, 26, %[s3]\n\t"                     /* r */                      \
   "v_xor_b32_e32 v3, 63, v2\n\t"                            /* 63 - r */                 \
@@ -436,7 +445,7 @@ constexpr bool negated(int c) {
 }
 
 // Draw schedule of a launch: the P streams grouped into interleaved pairs
-// (sa_draw2.h) wherever two streams touch disjoint accumulators (or, for
+// (sa_draw3.h) wherever two streams touch disjoint accumulators (or, for
 // two cross streams of one client, one shared accumulator), singles
 // otherwise.  Internal pairs of L clients are matched greedily
 // (for L = 8: 14 disjoint pairs of pairs), cross streams by client.
@@ -445,7 +454,7 @@ constexpr bool negated(int c) {
 // that ADDS to it (as the adding client u, or as a partner kept negated):
 // such a first touch writes the accumulator from the client's bias constant
 // (an SGPR pair) instead of reading it, so the tile presets no accumulator
-// with v_movs (sa_draw2.h, first-touch variants F).  A client first touched
+// with v_movs (sa_draw3.h, first-touch variants F).  A client first touched
 // as a subtracting partner or by a single draw (or never, P = 0) is preset
 // instead (`preset`); for every instantiated shape that set is empty or
 // holds only single-draw clients.
@@ -454,7 +463,7 @@ struct Group {
   int ua, va, ub, vb;  // accumulators: u adds t; v < 0: a cross stream (no partner)
   bool va_add, vb_add;  // the partner adds t (it is stored negated) instead of subtracting
   bool fa, fb;          // cross stream of a negated client: inverted sign mask
-  int F;                // first-touch bits: 1 ua, 2 va, 4 ub, 8 vb (sa_draw2.h template argument)
+  int F;                // first-touch bits: 1 ua, 2 va, 4 ub, 8 vb (sa_draw3.h template argument)
 };
 template <int L, int X, int K = kAllPairs>
 struct Sched {
@@ -634,7 +643,7 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
   // ---- prologue: park every stream one tile jump before S_{first+1}, the
   // state element `first` is drawn from: V = A^-J (S_{first+1} - inc*G_J)
   // 128-bit states: limbs 0-1 as one 64-bit VGPR pair (the draw's first
-  // mad writes it in place, sa_draw2.h), limbs 2 and 3 as 32-bit VGPRs
+  // mad writes it in place, sa_draw3.h), limbs 2 and 3 as 32-bit VGPRs
   struct State {
     uint64_t p01;
     uint32_t s2, s3;
@@ -687,7 +696,7 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
   }
 
   // 0 iff some raw PCG64 draw of this lane (or, for the paired draws, of its
-  // wave) was 0; the paired draws test per tile (sa_draw2.h, ZeroAcc)
+  // wave) was 0; the paired draws test per tile (sa_draw3.h, ZeroAcc)
   uint32_t zmin = 0xFFFFFFFFu;
   SA_TS(ts1);
 
@@ -813,7 +822,7 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
     // the raw == 0 tests, one lane mask per element slot k of the lane so
     // that a draw for an element past n (the wave's last tile draws for
     // every lane) is not counted: numpy draws exactly n
-    ZeroAcc zh[kE];   // the paired draws' (sa_draw2.h)
+    ZeroAcc zh[kE];   // the paired draws' (sa_draw3.h)
     uint64_t zs[kE];  // the single draws' (SA_PCG_DRAW_ASM)
 #pragma unroll
     for (int k = 0; k < kE; k++) {
@@ -886,7 +895,7 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
     {
       uint64_t z0 = (uint64_t)zh[0] | zs[0], z1 = (uint64_t)zh[1] | zs[1];
       static_assert(kE == 2, "one mask per element slot");
-      static_assert(std::is_same<ZeroAcc, uint64_t>::value, "sa_draw2.h's lane-mask form of the zero test");
+      static_assert(std::is_same<ZeroAcc, uint64_t>::value, "sa_draw3.h's lane-mask form of the zero test");
       if (__builtin_expect((z0 | z1) != 0, 0)) {
         if (base + wave_off + 64 * kE > n) {
           // the wave's last tile: lanes whose elements are >= n drew too.
@@ -1100,13 +1109,27 @@ int launch_clients(const KArgs& in, void* stream) {
       a.cbias[c] = negated<L>(c) ? (uint64_t)X - a.c[c].bias : a.c[c].bias;
     }
     const uint64_t tiles = (a.n + kTile - 1) / kTile;
-    const int grid = (int)(tiles < (uint64_t)maxb ? tiles : (uint64_t)maxb);
+    // The grid: enough blocks for the tiles, up to the cap, moved to the
+    // nearest grid whose tile-jump multiplier the three-carry draw is correct
+    // for (pcg128.h, qualifying_grid; blocks past the last tile run no
+    // iteration).
+    const int grid = qualifying_grid(tiles, maxb);
+    if (grid <= 0) {
+      sa_set_error("masking kernel: no grid of 1..%d blocks has a carry-free tile jump (three-carry draw)", maxb);
+      return SA_ERR_UNSUPPORTED;
+    }
     if (grid >= (1 << kGridBits)) {
       sa_set_error("masking kernel: grid of %d blocks exceeds the prologue's %d-bit block jump", grid, kGridBits);
       return SA_ERR_UNSUPPORTED;
     }
     // merged tile jump: S_{i+kE} -> S_{i+stride+1}, i.e. stride - kE + 1 draws
     const Jump jj = jump_of((uint64_t)grid * kTile - (kE - 1));
+    // the draw drops the carry out of its middle column: exact only for such
+    // a multiplier, so it is checked where the constants are made
+    if (!carry_free(jj.mult)) {
+      sa_set_error("masking kernel: the tile jump of a %d-block grid is not carry-free (three-carry draw)", grid);
+      return SA_ERR_UNSUPPORTED;
+    }
     a.aj_lo = lo64(jj.mult);
     a.aj_hi = hi64(jj.mult);
     const u128 aji = inv128(jj.mult);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build check of the draw's register aliasing (sa_draw2.h).
+"""Build check of the draw's register aliasing (sa_draw3.h).
 
 The draw keeps each state's limbs 0-1 in one 64-bit VGPR pair (asm operand
 p01) and reads them through two 32-bit input operands s0 / s1 that the
@@ -10,7 +10,7 @@ every kernel (hipcc -S / --save-temps) and checks, for every draw block,
 that each pair-writing mad reads its limb 0 from the pair's low register
 and that the limb-1 add updates the pair's high register in place.
 
-Run by the Makefile on every object that includes sa_draw2.h (the masking
+Run by the Makefile on every object that includes sa_draw3.h (the masking
 kernels) and by __graft_entry__.build() on tools/microbench/draw_issue (the
 draw-loop ceiling bench.py quotes).  The inline-asm contract cannot express
 "this 32-bit input is the low half of that 64-bit operand", so a new hipcc

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generates sfl_amd/csrc/sa_draw2.h: two PCG64 draws (two independent mask
+"""Generates sfl_amd/csrc/sa_draw2.h and, with --carry3, sa_draw3.h (the form
+the kernels include; see below): two PCG64 draws (two independent mask
 streams, same multiplier) as ONE hand-scheduled inline-asm block, their
 instruction streams interleaved so every dependent pair of one stream sits at
 least two issue slots apart (the other stream's instruction fills the gap).
@@ -47,7 +48,27 @@ that on the ISA of every build (the library's masking kernels and
 tools/microbench/draw_issue); a hipcc upgrade must pass it before its build
 is used, and a failing build leaves no object behind.
 
+Two headers come from this script.  The default output, sa_draw2.h, is the
+GENERAL-multiplier form: the weight-2^32 column O1 = s0*a1 + c1 + s1*a0 may
+exceed 64 bits, so the second O1 mad's carry-out is kept and the columns are
+joined by four carry adds.  It is pinned byte for byte by the tests and kept
+as the reference form for any multiplier; the kernels no longer include it.
+--carry3 emits sa_draw3.h, the form the kernels include (sfl_amd/csrc/Makefile
+writes it at build time; it is not committed): for a multiplier
+whose two low limbs satisfy a0 + a1 + 1 <= 2^32 (pcg128.h, carry_free) O1 is
+at most (2^32 - 1)(a0 + a1 + 1) < 2^64, that carry-out is always 0 and goes
+to the discard pair, and three carry adds join the columns
+    s1 = E0.hi + O1.lo -> cy;  s2 = E2.lo + O1.hi + cy -> cy;  s3 = E2.hi + L3 + cy
+-- one VALU fewer per draw.  PCG64's own multiplier qualifies; the merged
+tile jump's A^J does for the grids launch_clients picks (qualifying_grid),
+which checks the predicate on the host before every launch.  The tail is
+ordered so that a stream's dependent carries stay >= 3 slots apart without
+s_nop: the limb-3 chain's last mad (its discarded carry-out moved to the k2
+pair, free until the second join writes it) sits between the first two
+joins, the low v_bitop3 between the last two.
+
 usage: python tools/gen_draw2.py > sfl_amd/csrc/sa_draw2.h
+       python tools/gen_draw2.py --carry3 > sfl_amd/csrc/sa_draw3.h
 """
 
 import re
@@ -90,6 +111,11 @@ ROTS = not ROT64 and "--alignbit" not in sys.argv
 # per two draws, no SALU: for A/B (tools/microbench/draw_ops: a compare +
 # s_or_b64 pair issues at 7.5 cycles, the compare alone at 4.5).
 ZMIN_FORM = ROTS and "--zmin" in sys.argv
+# --carry3: the three-carry join for carry-free multipliers (see the
+# docstring), on the default form only.
+CARRY3 = "--carry3" in sys.argv
+if CARRY3 and not (PAIR01 and ROTS and not ZMIN_FORM):
+    sys.exit("gen_draw2.py: --carry3 is emitted for the default form only")
 
 # one draw: (asm, sgpr_writes, sgpr_reads); {..} fields are renamed per stream
 DRAW = [
@@ -175,6 +201,36 @@ def draw_steps():
     return DRAW[:i0] + ROT64_STEPS + DRAW[i1 + 1:]
 
 
+def carry3(draw):
+    """The pair01 draw with the three-carry join (O1 < 2^64: no kO)."""
+    def take(prefix):
+        hit = [s for s in draw if s[0].startswith(prefix)]
+        assert len(hit) == 1, prefix
+        return hit[0]
+    o1b = take("v_mad_u64_u32 v[{v2}:{v3}], %[{k2}]")
+    d3 = take("v_mad_u64_u32 v[{v6}:{v7}], %[{k3}], %[{s3}]")
+    j1 = take("v_add_co_u32_e64 %[{s1}]")
+    old2 = take("v_addc_co_u32_e64 %[{s3}], %[{k2}], v{v5}")
+    j2 = take("v_addc_co_u32_e64 %[{s2}]")
+    lo = take("v_bitop3_b32 v{v0}, %[{s0}]")
+    old4 = take("v_addc_co_u32_e64 %[{s3}], %[{k3}], %[{s3}], 0")
+    out = []
+    for s in draw:
+        if s is o1b:  # its carry-out is always 0: discarded
+            out.append((s[0].replace("%[{k2}]", "%[{k3}]", 1), {"k3"}, set()))
+        elif s in (d3, old2, j2, lo):
+            continue
+        elif s is j1:
+            # k3 carries the first join's carry across the limb-3 chain's last
+            # mad, whose discarded carry-out goes to k2 instead
+            out += [j1, (d3[0].replace("%[{k3}]", "%[{k2}]", 1), {"k2"}, set()), j2, lo]
+        elif s is old4:
+            out.append(("v_addc_co_u32_e64 %[{s3}], %[{k3}], v{v5}, v{v6}, %[{k2}]", {"k3"}, {"k2"}))
+        else:
+            out.append(s)
+    return out
+
+
 def stream(tag, base, vmode, acc_u, acc_v):
     """vmode: None (no second client), "s" (subtract) or "a" (add)."""
     f = {"s0": f"s0{tag}", "s1": f"s1{tag}", "s2": f"s2{tag}", "s3": f"s3{tag}",
@@ -214,6 +270,8 @@ def stream(tag, base, vmode, acc_u, acc_v):
             draw.append((asm, w, r))
             if asm.startswith("v_mad_u64_u32 v[{v6}:{v7}], %[{k3}], %[{s1}], %[a2]"):
                 draw.append(e0)  # after the last read of limbs 0 and 1
+    if CARRY3:
+        draw = carry3(draw)
     for asm, w, r in draw:
         if asm == "VADD":
             if vmode != "a":
@@ -367,9 +425,18 @@ def emit(name, vma, vmb, same_acc):
 
 
 def main():
-    print("// sa_draw2.h -- GENERATED by tools/gen_draw2.py; do not edit.")
+    if CARRY3:
+        print("// sa_draw3.h -- GENERATED by tools/gen_draw2.py --carry3; do not edit.")
+    else:
+        print("// sa_draw2.h -- GENERATED by tools/gen_draw2.py; do not edit.")
     print("// Two interleaved PCG64 draws per asm block (see the generator's docstring);")
     print("// operand conventions as pcg_draw_pair / pcg_draw_one in sa_clients_impl.h.")
+    if CARRY3:
+        print("// Three-carry form: CORRECT ONLY for a multiplier whose two low limbs satisfy")
+        print("// a0 + a1 + 1 <= 2^32 (pcg128.h, carry_free), so that the weight-2^32 column")
+        print("// s0*a1 + c1 + s1*a0 stays below 2^64 and its second mad's carry-out, always 0,")
+        print("// is discarded.  launch_clients checks that on the host for every launch;")
+        print("// sa_draw2.h is the four-carry form for any multiplier.")
     print("#pragma once")
     print("#include <stdint.h>")
     print()
@@ -382,6 +449,8 @@ def main():
     print("};")
     print()
     form = ("rots_zmin" if ZMIN_FORM else "rots") if ROTS else ("rot64" if ROT64 else "alignbit")
+    if CARRY3:
+        form += "_carry3"
     print(f'#define SA_DRAW2_FORM "{form}"')
     print()
     print("// The paired draws' running raw == 0 test (numpy re-draws a raw 0), kept per")

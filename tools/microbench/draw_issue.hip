@@ -32,7 +32,7 @@ struct StreamLds {
 typedef __attribute__((address_space(3))) const StreamLds* lds_ptr;
 
 // a draw state as the product kernel holds it: limbs 0-1 as one VGPR pair
-// (written in place by the paired draws, sa_draw2.h), limbs 2 and 3
+// (written in place by the paired draws, sa_draw3.h), limbs 2 and 3
 struct MbState {
   uint64_t p01;
   uint32_t s2, s3;

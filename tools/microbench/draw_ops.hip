@@ -1,5 +1,5 @@
 // Issue cost on gfx950 of every instruction form the PCG64 pair draw uses
-// (sa_draw2.h), as the draw writes it: VOP3 forms with SGPR carry-outs,
+// (sa_draw3.h), as the draw writes it: VOP3 forms with SGPR carry-outs,
 // SGPR carry-ins, SGPR lane masks.  8 independent chains per lane, 16
 // instructions per asm block, 8 waves per SIMD (2048 blocks of 256 on 256
 // CUs), so the figure is the SIMD's issue throughput for that form, not a
