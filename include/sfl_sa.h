@@ -692,6 +692,73 @@ int sa_quant_fp8(const void* x, int x_type, uint64_t n, double scale, int mant_l
 int sa_dequant_fp8(const void* q, uint64_t n, double scale, int mant_len, int exp_offset, int x_type, void* out,
                    void* stream);
 
+/* data_out[i] = x[index[i]], i < nnz: a tensor's values at a mask's
+ * positions, zeros included.  The mask is validated like a payload: an index
+ * outside [0, n) is never used as an address and sets SA_COO_BAD_RANGE, one
+ * not above its predecessor SA_COO_BAD_ORDER, flag[1] the least such i; the
+ * entries of data_out behind a flagged index are unspecified.  data_out may
+ * alias nothing. */
+int sa_coo_gather(const void* index, uint64_t nnz, const void* x, int x_type, uint64_t n, void* data_out, void* flag,
+                  void* stream);
+
+/* ------------------------------------------------------------------ */
+/* Top-k sparsification: the reference's TopkSparse and RandomSparse    */
+/* (sfl/utils/compressor/sparse_compressor.py:97-139).  Of n keys of    */
+/* key_type (SA_F32 or SA_F64) the k of largest magnitude are kept,     */
+/* ordered by the bit pattern of |key| as an unsigned integer (numpy's  */
+/* order, NaN last, so NaN is kept first).  Equal keys at the           */
+/* threshold: the HIGHER indices are kept, so the kept set is the       */
+/* complement of what sa_stc masks at mask_num = n - k.  The payload is */
+/* (index, data) as in the COO block: the kept flat positions as int32, */
+/* strictly ascending, and x at those positions, bit for bit.           */
+/*   sa_topk_select: sa_stc's radix select over keys for rank           */
+/*           n - k - 1 (one histogram pass and one one-block scan per   */
+/*           digit: 3 digits for float32, 6 for float64), one counting  */
+/*           pass (per wave: the keys above the threshold and the ties  */
+/*           at it) and one block that turns the tie counts into each   */
+/*           wave's first tie rank and the kept counts into exclusive   */
+/*           output offsets, all in scratch.  k == 0 and k == n skip    */
+/*           the digit passes.                                          */
+/*   sa_topk_fill: with the same keys, n, k and scratch, every wave     */
+/*           re-reads its range and stores index_out[rank] = e,         */
+/*           data_out[rank] = x[e]; ranks come from ballot prefixes     */
+/*           (no atomics, no sort).  x may be keys itself (one load) or */
+/*           another vector of n elements of x_type.  No entry of rank  */
+/*           >= k is stored; a total other than k (keys changed between */
+/*           the two calls) sets SA_COO_BAD_COUNT in flag, the two-word */
+/*           record of the COO entries.  index_out and data_out may     */
+/*           alias nothing.                                             */
+/*   sa_topk_random_keys: RandomSparse's keys, n 8-byte words.  Element */
+/*           e takes words w[2e], w[2e+1] of the Philox4x32-10 stream   */
+/*           under the 64-bit seed (counter block e >> 1 = (lo, hi, 0,  */
+/*           0), key words (seed lo, seed hi); words 0, 1 for even e,   */
+/*           2, 3 for odd e): key = ((w[2e+1] << 32) | w[2e]) >> 1, 63  */
+/*           bits.  Read as float64 bit patterns (key_type SA_F64) by   */
+/*           the two entries above, the k largest keys are k positions  */
+/*           drawn uniformly without replacement.                       */
+/*           sa_topk_random_keys_host: the same words in host memory,   */
+/*           no GPU needed.                                             */
+/* n >= 2^31, other element types and k > n are refused before any      */
+/* launch; n == 0 returns before the pointers are looked at.            */
+/* Everything is stream-ordered, allocates nothing, uses no float       */
+/* atomics and never synchronises with the host; the same input gives   */
+/* the same bits on every run.  16-byte aligned vectors take 16-byte    */
+/* loads.                                                               */
+/* ------------------------------------------------------------------ */
+
+/* bytes of device scratch the two entries share for n keys (8-byte aligned;
+ * sa_topk_select writes it, sa_topk_fill reads it), or a negative SA_ERR_* code */
+int sa_topk_scratch_bytes(uint64_t n, int key_type);
+
+int sa_topk_select(const void* keys, int key_type, uint64_t n, uint64_t k, void* scratch, void* stream);
+
+int sa_topk_fill(const void* keys, int key_type, const void* x, int x_type, uint64_t n, uint64_t k,
+                 const void* scratch, void* index_out, void* data_out, void* flag, void* stream);
+
+int sa_topk_random_keys(uint64_t seed, uint64_t n, void* keys_out, void* stream);
+
+int sa_topk_random_keys_host(uint64_t seed, uint64_t n, void* keys_out);
+
 #ifdef __cplusplus
 }
 #endif

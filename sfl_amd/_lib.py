@@ -38,6 +38,8 @@ EXPORTED = (
     "sa_pcg64_find_zero", "sa_stream_shift", "sa_xor_u64", "sa_stc_scratch_bytes", "sa_stc",
     "sa_scr_scratch_bytes", "sa_scr",
     "sa_coo_scratch_bytes", "sa_coo_count", "sa_coo_fill", "sa_coo_decode", "sa_coo_axpy", "sa_coo_finish",
+    "sa_coo_gather", "sa_topk_scratch_bytes", "sa_topk_select", "sa_topk_fill", "sa_topk_random_keys",
+    "sa_topk_random_keys_host",
     "sa_quant_scratch_bytes", "sa_quant_range", "sa_quant_affine", "sa_dequant_affine", "sa_quant_fp8",
     "sa_dequant_fp8",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
@@ -145,6 +147,12 @@ def _declare(lib):
     lib.sa_coo_decode.argtypes = [vp, vp, i32, u64, u64, vp, vp, vp]
     lib.sa_coo_axpy.argtypes = [vp, vp, i32, u64, dbl, vp, i32, u64, vp, vp]
     lib.sa_coo_finish.argtypes = [vp, i32, u64, dbl, vp]
+    lib.sa_coo_gather.argtypes = [vp, u64, vp, i32, u64, vp, vp, vp]
+    lib.sa_topk_scratch_bytes.argtypes = [u64, i32]
+    lib.sa_topk_select.argtypes = [vp, i32, u64, u64, vp, vp]
+    lib.sa_topk_fill.argtypes = [vp, i32, vp, i32, u64, u64, vp, vp, vp, vp, vp]
+    lib.sa_topk_random_keys.argtypes = [u64, u64, vp, vp]
+    lib.sa_topk_random_keys_host.argtypes = [u64, u64, vp]
     lib.sa_quant_scratch_bytes.argtypes = [u64, i32]
     lib.sa_quant_range.argtypes = [vp, i32, u64, vp, vp, vp]
     lib.sa_quant_affine.argtypes = [vp, i32, u64, i32, dbl, dbl, i32, i32, vp, i32, vp]
@@ -270,4 +278,15 @@ def chacha20_blocks_host(key: bytes, nonce: int, block0: int, n_blocks: int):
     m = (1 << 64) - 1
     check(lib().sa_chacha20_blocks_host(chacha_key_words(key), int(nonce) & m, int(block0) & m, n_blocks,
                                         out.ctypes.data_as(C.POINTER(C.c_uint32))), "sa_chacha20_blocks_host")
+    return out
+
+
+def topk_random_keys_host(seed: int, n: int):
+    """RandomSparse's 63-bit keys of ``n`` elements under ``seed`` as uint64, computed on the host
+    (sa_topk_random_keys_host: what sa_topk_random_keys writes on the device)."""
+    import numpy as np
+
+    out = np.empty(n, dtype=np.uint64)
+    check(lib().sa_topk_random_keys_host(int(seed) & ((1 << 64) - 1), n, out.ctypes.data_as(C.c_void_p)),
+          "sa_topk_random_keys_host")
     return out

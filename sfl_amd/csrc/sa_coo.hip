@@ -7,6 +7,8 @@
 //   decode  = zero the dense tensor, then a validated scatter
 //   sum     = one validated axpy per party into a dense accumulator, then one
 //             streaming division
+//   gather  = a tensor's values at a validated index vector (the sparse_mask
+//             path of sfl_amd/utils/sparse_compressor.py)
 //
 // A non-zero is decided on the bit pattern, (bits & ~sign) != 0.  The encode
 // is a compaction in the wave layout that sa_stc uses too (sa_compress.h):
@@ -177,6 +179,18 @@ __global__ void __launch_bounds__(kBlock) k_axpy(const int32_t* __restrict__ ind
   }
 }
 
+// data_out[i] = x[index[i]]: the values of a tensor at a mask's positions
+// (zeros included); the mask is validated like a payload
+template <class T>
+__global__ void __launch_bounds__(kBlock) k_gather(const int32_t* __restrict__ index, uint64_t nnz,
+                                                   const T* __restrict__ x, uint32_t n, T* __restrict__ data_out,
+                                                   uint32_t* flag) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nnz; i += (uint64_t)gridDim.x * kBlock) {
+    uint32_t at;
+    if (check_entry(index, i, n, flag, &at)) data_out[i] = x[at];
+  }
+}
+
 template <class A>
 __global__ void __launch_bounds__(kBlock) k_divide(A* acc, uint64_t n, uint64_t len, int vec, A d) {
   const Range w = wave_range(n, len);
@@ -325,6 +339,37 @@ extern "C" int sa_coo_axpy(const void* index, const void* data, int x_type, uint
   else
     hipLaunchKernelGGL((k_axpy<double, double>), grid, block, 0, s, idx, (const double*)data, nnz, (uint32_t)n, w,
                        (double*)acc, f);
+  SA_HIP_CHECK(hipGetLastError());
+  return SA_OK;
+}
+
+extern "C" int sa_coo_gather(const void* index, uint64_t nnz, const void* x, int x_type, uint64_t n, void* data_out,
+                             void* flag, void* stream) {
+  const int rc = check_type_n(x_type, n, "sa_coo_gather");
+  if (rc != SA_OK) return rc;
+  const uintptr_t esz = elem_size(x_type);
+  if (nnz > n) {
+    sa_set_error("sa_coo_gather: more entries than the tensor has elements");
+    return SA_ERR_ARG;
+  }
+  if (!flag || misaligned(flag, 4) || (nnz && (!index || !x || !data_out)) || misaligned(index, 4) ||
+      misaligned(x, esz) || misaligned(data_out, esz)) {
+    sa_set_error("sa_coo_gather: bad arguments (flag and, for nnz > 0, index, x and data_out are required; "
+                 "element-aligned vectors)");
+    return SA_ERR_ARG;
+  }
+  if (nnz == 0) return SA_OK;
+  const uintptr_t o = (uintptr_t)data_out, oe = o + nnz * esz;
+  if ((o < (uintptr_t)x + n * esz && (uintptr_t)x < oe) || (o < (uintptr_t)index + nnz * 4 && (uintptr_t)index < oe) ||
+      (o < (uintptr_t)flag + 8 && (uintptr_t)flag < oe)) {
+    sa_set_error("sa_coo_gather: data_out may alias nothing");
+    return SA_ERR_ARG;
+  }
+  dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL(k_gather<T>, dim3(entry_grid(nnz)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const int32_t*)index, nnz, (const T*)x, (uint32_t)n, (T*)data_out, (uint32_t*)flag);
+  });
   SA_HIP_CHECK(hipGetLastError());
   return SA_OK;
 }

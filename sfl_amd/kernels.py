@@ -613,7 +613,7 @@ def coo_flag(device) -> torch.Tensor:
     """A fresh flag record for ``coo_fill`` / ``coo_decode`` / ``coo_axpy``:
     no bit set, no offending position (``[0, -1]`` as int32)."""
     flag = torch.zeros(2, dtype=torch.int32, device=device)
-    flag[1] = -1
+    flag[1:].fill_(-1)  # a fill kernel: indexed assignment of a Python scalar copies it from the host
     return flag
 
 
@@ -699,6 +699,82 @@ def coo_finish(acc: torch.Tensor, divisor: float) -> torch.Tensor:
     L.check(L.lib().sa_coo_finish(_ptr(acc), at, acc.numel(), float(divisor), C.c_void_p(_stream(acc))),
             "sa_coo_finish")
     return acc
+
+
+def coo_gather(index: torch.Tensor, x: torch.Tensor, data_out: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """data_out[i] = x[index[i]]: a tensor's values at a mask's positions.  An
+    index outside the tensor is not used and goes into ``flag`` like a
+    payload's.  See sa_coo_gather in include/sfl_sa.h."""
+    _require_gpu(index, x, data_out, flag)
+    xt = _coo_payload("coo_gather", index, data_out)
+    if x.dtype != data_out.dtype or not x.is_contiguous():
+        raise ValueError("coo_gather: x is contiguous and has data_out's dtype")
+    if index.numel() > x.numel():
+        raise ValueError("coo_gather: more entries than the tensor has elements")
+    _coo_words("coo_gather", "flag", flag, 2)
+    L.check(L.lib().sa_coo_gather(_ptr(index), index.numel(), _ptr(x), xt, x.numel(), _ptr(data_out), _ptr(flag),
+                                  C.c_void_p(_stream(x))), "sa_coo_gather")
+    return data_out
+
+
+# ---------------------------------------------------------------------------
+# top-k sparsification (sa_topk_*; utils/sparse_compressor.py on top)
+# ---------------------------------------------------------------------------
+def topk_scratch_bytes(n: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``topk_select`` / ``topk_fill`` share for ``n`` keys of ``dtype``."""
+    return _scratch_bytes("topk_scratch_bytes", "sa_topk_scratch_bytes", (n,), dtype)
+
+
+def _topk_keys(what: str, keys: torch.Tensor, k: int, scratch: torch.Tensor) -> int:
+    kt = _float_xtype(what, keys.dtype)
+    if keys.dim() != 1 or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys is a flat contiguous tensor")
+    if not 0 <= int(k) <= keys.numel():
+        raise ValueError(f"{what}: k outside [0, n]")
+    _require_scratch(what, scratch, topk_scratch_bytes(keys.numel(), keys.dtype), "topk_scratch_bytes(n, dtype)")
+    return kt
+
+
+def topk_select(keys: torch.Tensor, k: int, scratch: torch.Tensor) -> None:
+    """The threshold of the ``k`` largest magnitudes of ``keys`` (ties: the
+    higher indices are kept) and every wave's tie and output ranks into
+    ``scratch``, for ``topk_fill``.  See sa_topk_select in include/sfl_sa.h."""
+    _require_gpu(keys, scratch)
+    kt = _topk_keys("topk_select", keys, k, scratch)
+    L.check(L.lib().sa_topk_select(_ptr(keys), kt, keys.numel(), int(k), _ptr(scratch), C.c_void_p(_stream(keys))),
+            "sa_topk_select")
+
+
+def topk_fill(keys: torch.Tensor, x: torch.Tensor, k: int, scratch: torch.Tensor, index_out: torch.Tensor,
+              data_out: torch.Tensor, flag: torch.Tensor) -> None:
+    """After ``topk_select`` of the same ``keys`` and ``k`` into the same
+    ``scratch``: the kept flat indices (int32, ascending) and ``x`` at them.
+    ``x`` is ``keys`` itself or another flat tensor of its length; a total
+    other than ``k`` sets ``SA_COO_BAD_COUNT`` in ``flag``."""
+    _require_gpu(keys, x, scratch, index_out, data_out, flag)
+    kt = _topk_keys("topk_fill", keys, k, scratch)
+    if x.dim() != 1 or x.numel() != keys.numel() or not x.is_contiguous():
+        raise ValueError("topk_fill: x is a flat contiguous tensor of keys' length")
+    if data_out.dtype != x.dtype:
+        raise ValueError("topk_fill: data_out has x's dtype")
+    xt = _coo_payload("topk_fill", index_out, data_out)
+    if index_out.numel() < int(k):
+        raise ValueError("topk_fill: index_out and data_out hold k entries")
+    _coo_words("topk_fill", "flag", flag, 2)
+    L.check(L.lib().sa_topk_fill(_ptr(keys), kt, _ptr(x), xt, keys.numel(), int(k), _ptr(scratch), _ptr(index_out),
+                                 _ptr(data_out), _ptr(flag), C.c_void_p(_stream(keys))), "sa_topk_fill")
+
+
+def topk_random_keys(seed: int, keys_out: torch.Tensor) -> torch.Tensor:
+    """RandomSparse's 63-bit keys under ``seed`` into ``keys_out`` (float64
+    or int64: 8-byte words), element ``e`` from the Philox words ``2e`` and
+    ``2e + 1``.  See sa_topk_random_keys in include/sfl_sa.h."""
+    _require_gpu(keys_out)
+    if keys_out.element_size() != 8 or keys_out.dim() != 1 or not keys_out.is_contiguous():
+        raise ValueError("topk_random_keys: keys_out is a flat contiguous tensor of 8-byte words")
+    L.check(L.lib().sa_topk_random_keys(int(seed) & 0xFFFFFFFFFFFFFFFF, keys_out.numel(), _ptr(keys_out),
+                                        C.c_void_p(_stream(keys_out))), "sa_topk_random_keys")
+    return keys_out
 
 
 # ---------------------------------------------------------------------------

@@ -37,6 +37,11 @@ The COO transport of what the two compressors produce (``sparse_encode`` /
 The quantized compressors for dense payloads (``QuantizedZeroPoint``,
 ``QuantizedLSTM``, ``QuantizedFP``, ``quantized_compressor.py:65-228``) live in
 ``sfl_amd.utils.quantized`` and are re-exported here too.
+
+``TopkSparse``, ``RandomSparse`` and ``MixedCompressor``
+(``sparse_compressor.py:23-139``, ``mixed_compressor.py:23-111``), the two base
+classes and the ``get(name, params)`` factory live in
+``sfl_amd.utils.sparse_compressor`` and are re-exported here as well.
 """
 
 from __future__ import annotations
@@ -296,3 +301,5 @@ class SCRSparse:
 from .sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode  # noqa: E402,F401
 from .quantized import (QuantizedCompressedData, QuantizedCompressor, QuantizedFP, QuantizedLSTM,  # noqa: E402,F401
                         QuantizedZeroPoint)
+from .sparse_compressor import (CompressedData, Compressor, MixedCompressedData, MixedCompressor,  # noqa: E402,F401
+                                RandomSparse, SparseCompressedData, SparseCompressor, SparseMask, TopkSparse, get)
