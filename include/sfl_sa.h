@@ -759,6 +759,75 @@ int sa_topk_random_keys(uint64_t seed, uint64_t n, void* keys_out, void* stream)
 
 int sa_topk_random_keys_host(uint64_t seed, uint64_t n, void* keys_out);
 
+/* ------------------------------------------------------------------ */
+/* QuantizedKmeans: the reference's class (sfl/utils/compressor/        */
+/* quantized_compressor.py:231-279) with the fit pinned, a 1-D k-means  */
+/* run in integers (sfl_amd/utils/quantized.py has the definition).     */
+/* A tensor of n elements of x_type T (SA_F32 or SA_F64), n < 2^32, is  */
+/* seen through its 32-bit image                                        */
+/*   u = min(2^32 - 1, uint64(rint((double(x) - mn) * s)))              */
+/* with host scalars mn and s = (2^32 - 1) / (mx - mn); the subtraction */
+/* and the multiplication round separately, never fused.  Every entry   */
+/* computes the image anew; nothing of it is stored.                    */
+/*   sa_kmeans_hist    hist[b] = the number of u with u >> 20 == b,     */
+/*           SA_KMEANS_BINS uint32 on the device (zeroed by the call):  */
+/*           what the host forms the start from                         */
+/*           (quantized_compressor.py:231-279 starts at random).        */
+/*   sa_kmeans_step    `steps` Lloyd steps on the state block, enqueued */
+/*           back to back (quantized_compressor.py:231-279: the fit).   */
+/*           The state, SA_KMEANS_STATE_BYTES on the device, 8-byte     */
+/*           aligned, written by the caller before the first step:      */
+/*             uint64 sum[256]; uint32 cnt[256]; uint32 c[256];         */
+/*             uint32 done, n_iter;                                     */
+/*           all zero but the k sorted centres c[0 .. k-1]              */
+/*           (SA_KMEANS_STATE_C bytes in; done at SA_KMEANS_STATE_DONE, */
+/*           n_iter behind it).  A step: b_j = (c_j + c_{j+1}) >> 1;    */
+/*           label(u) = the number of j with b_j < u; cnt_j and sum_j   */
+/*           over the labels; c'_j = sum_j / cnt_j rounded half up, an  */
+/*           empty cluster keeps c_j; n_iter += 1; done = 1 if no       */
+/*           centre moved.  A step that finds done set does nothing.    */
+/*           Counts and sums are integers added with integer atomics:   */
+/*           order-free, so the same input gives the same bits.         */
+/*   sa_kmeans_labels  q_out[i] = label(u_i) - offset under the state's */
+/*           centres, as q_bytes-byte codes (1: int8, 2: int16) in      */
+/*           sa_quant_affine's layout (quantized_compressor.py:231-279: */
+/*           labels_ - 2^(quant_bits-1)).                               */
+/*   sa_dequant_lut    out[i] = lut[q[i] + offset], lut k values of T   */
+/*           on the device, in sa_dequant_affine's layout               */
+/*           (quantized_compressor.py:231-279: _decompress_one).  The   */
+/*           codes are another party's data: one whose label is outside */
+/*           [0, k) is never used as an index, gives 0 and reports into */
+/*           flag, two uint32 the caller sets to {0, 0xffffffff}:       */
+/*           [0] |= SA_KMEANS_BAD_CODE, [1] the least such i.           */
+/* Other element types, n >= 2^32, k outside 2 .. SA_KMEANS_MAX_K, an   */
+/* offset that lets a code leave its storage type and misaligned        */
+/* pointers are refused before any launch.  x outside [mn, mx] images   */
+/* to 0 or 2^32 - 1; every store lands inside its output.  Everything   */
+/* is stream-ordered, allocates nothing, uses no float atomics and      */
+/* never synchronises with the host.                                    */
+/* ------------------------------------------------------------------ */
+#define SA_KMEANS_MAX_K 256
+#define SA_KMEANS_BINS 4096
+#define SA_KMEANS_STATE_BYTES 4104
+#define SA_KMEANS_STATE_C 3072
+#define SA_KMEANS_STATE_DONE 4096
+#define SA_KMEANS_BAD_CODE 1u /* a code whose label is outside [0, k) */
+
+/* bytes of device scratch a fit needs for n elements: the histogram, then the
+ * state block (8-byte aligned), or a negative SA_ERR_* code */
+int sa_kmeans_scratch_bytes(uint64_t n, int x_type);
+
+int sa_kmeans_hist(const void* x, int x_type, uint64_t n, double mn, double s, void* hist, void* stream);
+
+int sa_kmeans_step(const void* x, int x_type, uint64_t n, double mn, double s, int k, int steps, void* state,
+                   void* stream);
+
+int sa_kmeans_labels(const void* x, int x_type, uint64_t n, double mn, double s, int k, const void* state, int offset,
+                     void* q_out, int q_bytes, void* stream);
+
+int sa_dequant_lut(const void* q, int q_bytes, uint64_t n, const void* lut, int k, int offset, int x_type, void* out,
+                   void* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ SA_UNIQUE_ID_BYTES = 128
 SA_DP_PARTIALS = 1024
 SA_COO_BAD_RANGE, SA_COO_BAD_ORDER, SA_COO_BAD_COUNT = 1, 2, 4
 SA_QUANT_ZERO_POINT, SA_QUANT_LSTM = 0, 1
+SA_KMEANS_MAX_K, SA_KMEANS_BINS, SA_KMEANS_BAD_CODE = 256, 4096, 1
+SA_KMEANS_STATE_BYTES, SA_KMEANS_STATE_C, SA_KMEANS_STATE_DONE = 4104, 3072, 4096
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -42,6 +44,7 @@ EXPORTED = (
     "sa_topk_random_keys_host",
     "sa_quant_scratch_bytes", "sa_quant_range", "sa_quant_affine", "sa_dequant_affine", "sa_quant_fp8",
     "sa_dequant_fp8",
+    "sa_kmeans_scratch_bytes", "sa_kmeans_hist", "sa_kmeans_step", "sa_kmeans_labels", "sa_dequant_lut",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
 )
 
@@ -159,6 +162,11 @@ def _declare(lib):
     lib.sa_dequant_affine.argtypes = [vp, i32, u64, i32, dbl, dbl, i32, vp, vp]
     lib.sa_quant_fp8.argtypes = [vp, i32, u64, dbl, i32, i32, vp, vp]
     lib.sa_dequant_fp8.argtypes = [vp, u64, dbl, i32, i32, i32, vp, vp]
+    lib.sa_kmeans_scratch_bytes.argtypes = [u64, i32]
+    lib.sa_kmeans_hist.argtypes = [vp, i32, u64, dbl, dbl, vp, vp]
+    lib.sa_kmeans_step.argtypes = [vp, i32, u64, dbl, dbl, i32, i32, vp, vp]
+    lib.sa_kmeans_labels.argtypes = [vp, i32, u64, dbl, dbl, i32, vp, i32, vp, i32, vp]
+    lib.sa_dequant_lut.argtypes = [vp, i32, u64, vp, i32, i32, i32, vp, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -923,3 +923,76 @@ def stream_shifts(out: torch.Tensor, gen, sign: int, pts: Sequence[tuple]) -> to
     for k, shift in pts:
         stream_shift(out, gen, sign, k, shift)
     return out
+
+
+# ---------------------------------------------------------------------------
+# QuantizedKmeans (sa_kmeans_*, sa_dequant_lut; utils/quantized.py on top)
+# ---------------------------------------------------------------------------
+def kmeans_scratch_bytes(n: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch a fit of ``n`` elements of ``dtype`` needs: the
+    histogram (``SA_KMEANS_BINS`` words), then the state block."""
+    return _scratch_bytes("kmeans_scratch_bytes", "sa_kmeans_scratch_bytes", (n,), dtype)
+
+
+def _kmeans_x(what: str, x: torch.Tensor, k: int | None = None) -> int:
+    _require_gpu(x)
+    xt = _float_xtype(what, x.dtype)
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: a contiguous tensor")
+    if k is not None and not 2 <= int(k) <= L.SA_KMEANS_MAX_K:
+        raise ValueError(f"{what}: k must be in 2..{L.SA_KMEANS_MAX_K}, got {k}")
+    return xt
+
+
+def _kmeans_state(what: str, state: torch.Tensor) -> None:
+    _require_gpu(state)
+    if state.numel() * state.element_size() < L.SA_KMEANS_STATE_BYTES or not state.is_contiguous() \
+            or state.data_ptr() % 8:
+        raise ValueError(f"{what}: the state is {L.SA_KMEANS_STATE_BYTES} contiguous, 8-byte aligned bytes")
+
+
+def kmeans_hist(x: torch.Tensor, mn: float, s: float, hist: torch.Tensor) -> torch.Tensor:
+    """The 4096-bin histogram of the image of ``x`` into ``hist`` (int32 words
+    that carry uint32 counts).  See sa_kmeans_hist in include/sfl_sa.h."""
+    xt = _kmeans_x("kmeans_hist", x)
+    _require_gpu(hist)
+    _coo_words("kmeans_hist", "hist", hist, L.SA_KMEANS_BINS)
+    L.check(L.lib().sa_kmeans_hist(_ptr(x), xt, x.numel(), float(mn), float(s), _ptr(hist), C.c_void_p(_stream(x))),
+            "sa_kmeans_hist")
+    return hist
+
+
+def kmeans_step(x: torch.Tensor, mn: float, s: float, k: int, steps: int, state: torch.Tensor) -> torch.Tensor:
+    """``steps`` Lloyd steps on ``state``, enqueued back to back; a step after
+    the one that moved no centre does nothing.  See sa_kmeans_step."""
+    xt = _kmeans_x("kmeans_step", x, k)
+    _kmeans_state("kmeans_step", state)
+    L.check(L.lib().sa_kmeans_step(_ptr(x), xt, x.numel(), float(mn), float(s), int(k), int(steps), _ptr(state),
+                                   C.c_void_p(_stream(x))), "sa_kmeans_step")
+    return state
+
+
+def kmeans_labels(x: torch.Tensor, mn: float, s: float, k: int, state: torch.Tensor, offset: int,
+                  q_out: torch.Tensor) -> torch.Tensor:
+    """``q_out`` (int8 / int16) = the label of every element under the state's
+    centres, minus ``offset``.  See sa_kmeans_labels."""
+    xt, qb = _quant_pair("kmeans_labels", x, q_out)
+    _kmeans_x("kmeans_labels", x, k)
+    _kmeans_state("kmeans_labels", state)
+    L.check(L.lib().sa_kmeans_labels(_ptr(x), xt, x.numel(), float(mn), float(s), int(k), _ptr(state), int(offset),
+                                     _ptr(q_out), qb, C.c_void_p(_stream(x))), "sa_kmeans_labels")
+    return q_out
+
+
+def dequant_lut(q: torch.Tensor, lut: torch.Tensor, offset: int, out: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """``out[i] = lut[q[i] + offset]``; a label outside ``[0, len(lut))`` gives
+    0 and goes into ``flag`` (a ``coo_flag`` record).  See sa_dequant_lut."""
+    xt, qb = _quant_pair("dequant_lut", out, q)
+    _require_gpu(lut, flag)
+    k = lut.numel()
+    if lut.dtype != out.dtype or not lut.is_contiguous() or not 2 <= k <= L.SA_KMEANS_MAX_K:
+        raise ValueError(f"dequant_lut: lut is 2..{L.SA_KMEANS_MAX_K} contiguous values of the output's dtype")
+    _coo_words("dequant_lut", "flag", flag, 2)
+    L.check(L.lib().sa_dequant_lut(_ptr(q), qb, q.numel(), _ptr(lut), k, int(offset), xt, _ptr(out), _ptr(flag),
+                                   C.c_void_p(_stream(out))), "sa_dequant_lut")
+    return out

@@ -35,7 +35,8 @@ The COO transport of what the two compressors produce (``sparse_encode`` /
 ``sfl_amd.utils.sparse`` and is re-exported here.
 
 The quantized compressors for dense payloads (``QuantizedZeroPoint``,
-``QuantizedLSTM``, ``QuantizedFP``, ``quantized_compressor.py:65-228``) live in
+``QuantizedLSTM``, ``QuantizedFP``, ``QuantizedKmeans``,
+``quantized_compressor.py:65-279``) live in
 ``sfl_amd.utils.quantized`` and are re-exported here too.
 
 ``TopkSparse``, ``RandomSparse`` and ``MixedCompressor``
@@ -299,7 +300,7 @@ class SCRSparse:
 
 
 from .sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode  # noqa: E402,F401
-from .quantized import (QuantizedCompressedData, QuantizedCompressor, QuantizedFP, QuantizedLSTM,  # noqa: E402,F401
-                        QuantizedZeroPoint)
+from .quantized import (KmeansCompressData, QuantizedCompressedData, QuantizedCompressor, QuantizedFP,  # noqa: E402,F401
+                        QuantizedKmeans, QuantizedLSTM, QuantizedZeroPoint)
 from .sparse_compressor import (CompressedData, Compressor, MixedCompressedData, MixedCompressor,  # noqa: E402,F401
                                 RandomSparse, SparseCompressedData, SparseCompressor, SparseMask, TopkSparse, get)

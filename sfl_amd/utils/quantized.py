@@ -75,6 +75,54 @@ So ``scale``, ``z``, ``q`` and ``rqm`` are host scalars as in the reference, and
 host and device can differ only in ``min`` / ``max`` or the per-element kernel.
 ``decompress`` reads nothing back.  On the device ``quant_bits > 16`` is
 refused (host arrays take any width).
+
+``QuantizedKmeans`` (``quantized_compressor.py:231-279``): a 1-D k-means whose
+labels are the codes and whose centres ``q`` decode them.  The reference fits
+scikit-learn's randomly initialised ``KMeans(K, n_init=1, max_iter=50)``; here
+the fit is pinned.  ``n`` is the element count, ``K < n < 2^32``;
+``K = n_clusters`` (default ``quant_bits``, as the reference),
+``2 <= K <= 2^quant_bits``; ``U = 2^32 - 1``; all integer arithmetic is
+unsigned 64-bit and floors.
+
+1. Range and image.  ``mn, mx = min(x), max(x)`` (NaN-propagating).  In
+   float64 ``s = U / (mx - mn)`` and ``step = (mx - mn) / U``;
+   ``u_i = min(U, uint64(rint((float64(x_i) - float64(mn)) * s)))``, the
+   subtraction and the multiplication rounded separately (never an FMA).
+2. Start, ``init="cbrt"`` (Panter-Dite: the quantiles of the cube root of the
+   density).  ``h[b]`` counts the ``u`` with ``u >> 20 == b``, 4096 bins;
+   ``w[b] = icbrt(h[b] << 30)``, the exact integer cube root; ``W`` its
+   inclusive prefix sum, ``tot = W[4095]``, ``W[-1] = 0``.  For ``j`` in
+   ``0..K-1``: ``r = ((2j+1) * tot) // (2K)``; ``b`` the first bin with
+   ``W[b] > r``; ``c_j = (b << 20) + (((r - W[b-1]) << 20) // w[b])``
+   (``kmeans_init(h, K)``, host code for both forms).  ``init`` may also be an
+   array of ``K`` non-decreasing centres of type ``T``, imaged by step 1 and
+   clipped to ``[0, U]`` (a warm start).  ``init=None`` is refused.
+3. Step.  ``b_j = (c_j + c_{j+1}) >> 1``; ``label(u)`` is the number of ``j``
+   with ``b_j < u`` (an element on a boundary belongs to the lower cluster);
+   ``cnt_j`` and ``sum_j`` run over the labels;
+   ``c'_j = sum_j // cnt_j + (2 * (sum_j % cnt_j) >= cnt_j)``; an empty
+   cluster keeps ``c_j``.  ``n_iter`` counts steps; the fit stops after the
+   step in which ``c' == c`` for all clusters, or after ``max_iter`` steps.
+4. Payload.  The labels under the final centres, ``code = label - 2^(bits-1)``
+   in the storage type and the data's shape;
+   ``q[j] = T(float64(mn) + float64(c_j) * step)``, a host array ``(K, 1)``
+   like ``cluster_centers_``; ``KmeansCompressData`` also carries ``n_iter``.
+5. ``n <= K`` passes the tensor through (``origin_type=None``, ``q=None``).
+   ``decompress`` gives ``q[code + 2^(bits-1)]`` as ``T``; a code outside
+   ``[0, K)`` is never used as an index: ``ValueError`` with the least such
+   position.
+
+Refused with ``_refuse``'s wording: a NaN, an inf, ``mx - mn`` not finite and
+positive in float64 (or so small that ``s`` overflows), an empty tensor.
+Refinements against the reference: the deterministic start; the integer image
+(float32 values below ``range * 2^-32`` and float64 resolution beyond 32 bits
+are lost); ``K > 2^quant_bits`` is refused where the reference wraps the
+labels; an empty cluster keeps its centre where scikit-learn relocates it; the
+stop is exact where scikit-learn stops at ``tol = 1e-4 * var``.  On the device
+(``sa_kmeans_*``, ``sfl_amd/csrc/sa_kmeans.hip``): ``K <= 256``,
+``quant_bits <= 16``; three pinned reads (the range, the histogram, the
+centres with ``n_iter``), ``max_iter`` steps enqueued back to back; host and
+device give the same codes, ``q`` and ``n_iter``.
 """
 
 from __future__ import annotations
@@ -492,4 +540,203 @@ class QuantizedFP(QuantizedCompressor):
             mant = ((a % ml).astype(T) / T(ml) + T(1)) / T(2)
             with np.errstate(all="ignore"):
                 dec = np.sign(codes).astype(T) * np.ldexp(mant, a // ml - off) / scale
+        return _unwrap(dec, tuple(c.compressed_data.shape), was_tensor)
+
+
+# ---------------------------------------------------------------------------
+# QuantizedKmeans: a pinned 1-D k-means (the module's docstring has the definition)
+# ---------------------------------------------------------------------------
+KMEANS_U = (1 << 32) - 1  # the image's largest value
+KMEANS_BINS, KMEANS_BIN_SHIFT = 4096, 20  # the start's histogram: u >> 20
+KMEANS_DEVICE_MAX_K = 256
+
+
+class KmeansCompressData(QuantizedCompressedData):
+    """``q``: the centres, a host array ``(K, 1)`` of the data's type (the
+    reference's ``cluster_centers_``); ``n_iter``: the steps the fit took.  A
+    tensor that passed through (``n <= K``) has ``origin_type`` and ``q`` None."""
+
+    _scalars = ("q", "n_iter")
+
+    def __init__(self, compressed_data, quant_bits, origin_type=None, q=None, n_iter=0):
+        super().__init__(compressed_data, quant_bits, origin_type)
+        self.q = q
+        self.n_iter = n_iter
+
+
+def kmeans_scale(mn, mx, name: str = "[0]"):
+    """``(mn, s, step)`` as float64 from ``min`` and ``max`` (numpy scalars of the data's type)."""
+    with np.errstate(all="ignore"):
+        lo, width = np.float64(mn), np.float64(mx) - np.float64(mn)
+        s, step = np.float64(KMEANS_U) / width, width / np.float64(KMEANS_U)
+        if not (np.isfinite(width) and width > 0 and np.isfinite(s)):
+            raise _refuse(name, "the range max - min is not finite and positive, or too small to divide by: a NaN, "
+                                "an inf, a constant tensor, a single element or no element at all")
+    return lo, s, step
+
+
+def kmeans_image(x: np.ndarray, mn, s) -> np.ndarray:
+    """The image ``u`` of ``x`` as uint64: subtract, multiply, ``rint``, clip to ``U``, each rounded in float64."""
+    with np.errstate(all="ignore"):
+        v = np.rint((x.astype(np.float64) - mn) * s)
+        return np.clip(v, 0.0, np.float64(KMEANS_U)).astype(np.uint64)
+
+
+def _icbrt(v: np.ndarray) -> np.ndarray:
+    """The exact integer cube root of uint64 values below 2^62."""
+    w = np.floor(np.cbrt(v.astype(np.float64))).astype(np.uint64)
+    w = np.where(w * w * w > v, w - np.uint64(1), w)  # the float root is within one of the integer root
+    return np.where((w + np.uint64(1)) ** 3 <= v, w + np.uint64(1), w)
+
+
+def kmeans_init(h, K: int) -> np.ndarray:
+    """The ``"cbrt"`` start from the histogram ``h`` (4096 counts of
+    ``u >> 20``): ``K`` sorted centres as uint64, the ``(2j+1) / 2K`` quantiles
+    of the cube root of the density, interpolated inside their bin."""
+    h = np.asarray(h).astype(np.uint64)
+    if h.shape != (KMEANS_BINS,):
+        raise ValueError(f"kmeans_init: the histogram has {KMEANS_BINS} bins")
+    w = _icbrt(h << np.uint64(30))
+    W = np.cumsum(w, dtype=np.uint64)  # below 2^33; (2K - 1) * tot and (r - below) << 20 stay far below 2^64
+    r = (np.arange(1, 2 * K, 2, dtype=np.uint64) * W[-1]) // np.uint64(2 * K)
+    b = np.searchsorted(W, r, side="right")  # the first bin with W[b] > r
+    below = np.where(b > 0, W[np.maximum(b, 1) - 1], np.uint64(0))
+    shift = np.uint64(KMEANS_BIN_SHIFT)
+    return (b.astype(np.uint64) << shift) + ((r - below) << shift) // w[b]
+
+
+def kmeans_update(c: np.ndarray, cnt: np.ndarray, total: np.ndarray) -> np.ndarray:
+    """``c'``: every cluster's sum over its count, rounded half up; an empty cluster keeps its centre."""
+    one = np.maximum(cnt, np.uint64(1))
+    quo, rem = total // one, total % one
+    return np.where(cnt > 0, quo + (np.uint64(2) * rem >= one).astype(np.uint64), c)
+
+
+def kmeans_centres(c: np.ndarray, mn, step, T) -> np.ndarray:
+    """``q``: the centres back in the data's type, ``(K, 1)``."""
+    return (mn + c.astype(np.float64) * step).astype(T).reshape(-1, 1)
+
+
+class QuantizedKmeans(QuantizedCompressor):
+    """The reference's ``QuantizedKmeans`` (arXiv:1510.00149) with a pinned
+    fit: integer Lloyd steps from a deterministic start; the module's
+    docstring has the definition.  ``init`` is ``"cbrt"`` or an array of
+    ``n_clusters`` non-decreasing centres; ``None``, the reference's random
+    start, is refused."""
+
+    KmeansCompressData = KmeansCompressData
+
+    def __init__(self, quant_bits: int = 8, n_clusters=None, init=None, max_iter: int = 50):
+        super().__init__(quant_bits)
+        self.n_clusters = K = int(quant_bits if n_clusters is None else n_clusters)
+        if K < 2 or K > (1 << quant_bits):
+            raise ValueError(f"QuantizedKmeans: n_clusters must be in 2..2^quant_bits = {1 << quant_bits}, got {K}: "
+                             "a label beyond 2^quant_bits has no code")
+        if init is None:
+            raise ValueError("QuantizedKmeans: init=None, scikit-learn's random start, is not built; pass "
+                             "init='cbrt' or an array of n_clusters sorted centres")
+        if isinstance(init, str):
+            if init != "cbrt":
+                raise ValueError(f"QuantizedKmeans: init is 'cbrt' or an array of centres, not {init!r}")
+        else:
+            init = np.asarray(_host(init) if isinstance(init, torch.Tensor) else init).reshape(-1)
+            if init.size != K or init.dtype.kind != "f" or not np.all(init[1:] >= init[:-1]):
+                raise ValueError(f"QuantizedKmeans: init as an array is {K} non-decreasing floating-point centres")
+        if int(max_iter) < 1:
+            raise ValueError(f"QuantizedKmeans: max_iter must be at least 1, got {max_iter}")
+        self.init, self.max_iter = init, int(max_iter)
+
+    def _start(self, hist, mn, s) -> np.ndarray:
+        """The first centres as uint64; ``hist`` gives the histogram when the start needs it."""
+        if isinstance(self.init, str):
+            return kmeans_init(hist(), self.n_clusters)
+        return kmeans_image(self.init, mn, s)
+
+    def _compress_one(self, data, name="[0]"):
+        K, bits = self.n_clusters, self.quant_bits
+        w = _Where(data, name, "QuantizedKmeans")
+        self._device_bits(w, name)
+        n = w.flat.numel() if w.device is not None else w.flat.size
+        if n == 0:
+            raise _refuse(name, "no element at all")
+        if n <= K:
+            return KmeansCompressData(data, bits)  # as the reference: too few elements to cluster
+        if n >> 32:
+            raise ValueError(f"QuantizedKmeans: entry {name} has 2^32 elements or more")
+        if w.device is not None and K > KMEANS_DEVICE_MAX_K:
+            raise ValueError(f"QuantizedKmeans: entry {name} is a device tensor, which takes n_clusters <= "
+                             f"{KMEANS_DEVICE_MAX_K} (got {K}); host arrays take any")
+        mn, mx, _ = w.range()
+        mn, s, step = kmeans_scale(mn, mx, name)
+        fit = self._fit_device if w.device is not None else self._fit_host
+        codes, c, n_iter = fit(w, mn, s)
+        return KmeansCompressData(codes, bits, w.dtype, kmeans_centres(c, mn, step, w.dtype.type), n_iter)
+
+    def _fit_host(self, w: _Where, mn, s):
+        K, half = self.n_clusters, 1 << (self.quant_bits - 1)
+        u = kmeans_image(w.flat, mn, s)
+        c = self._start(lambda: np.bincount((u >> np.uint64(KMEANS_BIN_SHIFT)).astype(np.int64),
+                                            minlength=KMEANS_BINS), mn, s)
+        lo, hi = (u & np.uint64(0xFFFF)).astype(np.float64), (u >> np.uint64(16)).astype(np.float64)
+        n_iter = 0
+        while n_iter < self.max_iter:
+            label = np.searchsorted((c[:-1] + c[1:]) >> np.uint64(1), u, side="left")
+            cnt = np.bincount(label, minlength=K).astype(np.uint64)
+            # the sums in two 16-bit halves: each half's float64 sum stays below 2^48, so it is exact
+            total = (np.bincount(label, weights=hi, minlength=K).astype(np.uint64) << np.uint64(16)) \
+                + np.bincount(label, weights=lo, minlength=K).astype(np.uint64)
+            new = kmeans_update(c, cnt, total)
+            n_iter += 1
+            same = np.array_equal(new, c)
+            c = new
+            if same:
+                break
+        label = np.searchsorted((c[:-1] + c[1:]) >> np.uint64(1), u, side="left")
+        return w.wrap((label - half).astype(self.np_type)), c, n_iter
+
+    def _fit_device(self, w: _Where, mn, s):
+        from .. import _lib as L
+        from .. import hostpipe as H
+        from .. import kernels as Kn
+        from .compressor import _scratch_for
+
+        K, x = self.n_clusters, w.flat
+        scratch = _scratch_for(x, Kn.kmeans_scratch_bytes(x.numel(), x.dtype))  # the histogram, then the state
+        hist = scratch[:4 * KMEANS_BINS].view(torch.int32)
+        state = scratch[4 * KMEANS_BINS:4 * KMEANS_BINS + L.SA_KMEANS_STATE_BYTES]
+        c0 = self._start(lambda: H.d2h(Kn.kmeans_hist(x, mn, s, hist), pooled=False).view(np.uint32), mn, s)
+        words = np.zeros(L.SA_KMEANS_STATE_BYTES // 4, dtype=np.uint32)
+        words[L.SA_KMEANS_STATE_C // 4:][:K] = c0
+        state.copy_(H.h2d(words.view(np.uint8), x.device))
+        Kn.kmeans_step(x, mn, s, K, self.max_iter, state)
+        codes = Kn.kmeans_labels(x, mn, s, K, state, 1 << (self.quant_bits - 1), w.codes(self.np_type))
+        tail = H.d2h(state[L.SA_KMEANS_STATE_C:].view(torch.int32), pooled=False).view(np.uint32)
+        n_iter = int(tail[(L.SA_KMEANS_STATE_DONE - L.SA_KMEANS_STATE_C) // 4 + 1])
+        return codes.reshape(w.shape), tail[:K].astype(np.uint64), n_iter
+
+    def _decompress_one(self, c, name="[0]"):
+        if c.q is None:  # passed through
+            return c.compressed_data
+        codes, on_device, was_tensor = _codes_of(c, _store_type(c.quant_bits), name, "QuantizedKmeans")
+        T, half = c.origin_type.type, 1 << (c.quant_bits - 1)
+        q = np.ascontiguousarray(np.asarray(c.q).reshape(-1), dtype=T)
+        K = q.size
+        if on_device:
+            from .. import hostpipe as H
+            from .. import kernels as Kn
+
+            out = torch.empty(codes.numel(), dtype=_torch_dtype(c.origin_type), device=codes.device)
+            bad, at = 0, 0
+            if codes.numel():
+                flag = Kn.coo_flag(codes.device)
+                Kn.dequant_lut(codes, H.h2d(q, codes.device), half, out, flag)
+                bad, at = (int(v) for v in H.d2h(flag, pooled=False).view(np.uint32))
+            dec = out
+        else:
+            label = codes.astype(np.int64) + half
+            wrong = (label < 0) | (label >= K)
+            bad, at = bool(wrong.any()), int(np.argmax(wrong))
+            dec = None if bad else q[label]
+        if bad:
+            raise ValueError(f"QuantizedKmeans: entry {name} holds a code outside the {K} clusters at position {at}")
         return _unwrap(dec, tuple(c.compressed_data.shape), was_tensor)

@@ -466,7 +466,7 @@ def get(name: str, params: Union[Dict, List, None]):
     keyword arguments; ``"mixed_compressor"`` takes a list of
     ``{"name": ..., "params": ...}``."""
     from .compressor import SCRSparse, STCSparse
-    from .quantized import QuantizedFP, QuantizedLSTM, QuantizedZeroPoint
+    from .quantized import QuantizedFP, QuantizedKmeans, QuantizedLSTM, QuantizedZeroPoint
 
     simple = {"random_sparse": RandomSparse, "topk_sparse": TopkSparse, "stc_sparse": STCSparse,
               "scr_sparse": SCRSparse, "quantized_fp": QuantizedFP, "quantized_lstm": QuantizedLSTM,
@@ -474,8 +474,10 @@ def get(name: str, params: Union[Dict, List, None]):
     if name in simple:
         return simple[name](**(params or {}))
     if name == "quantized_kmeans":
-        raise ValueError("Compressor 'quantized_kmeans' is not built: scikit-learn's randomly initialised k-means "
-                         "has no definition to pin")
+        if (params or {}).get("init") is None:
+            raise ValueError("Compressor 'quantized_kmeans' is not built: scikit-learn's randomly initialised "
+                             "k-means has no definition to pin; pass init='cbrt'")
+        return QuantizedKmeans(**params)
     if name == "mixed_compressor":
         assert isinstance(params, list)
         parts = []
