@@ -828,6 +828,69 @@ int sa_kmeans_labels(const void* x, int x_type, uint64_t n, double mn, double s,
 int sa_dequant_lut(const void* q, int q_bytes, uint64_t n, const void* lut, int k, int offset, int x_type, void* out,
                    void* flag, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* FlameAggregator: the per-element work of the reference's robust      */
+/* aggregator (examples/security/h_bd/agg_flame.py:27-203) for C        */
+/* clients, 1 <= C <= SA_FLAME_MAX_CLIENTS, whose tensors of n elements */
+/* of x_type T (SA_F32 or SA_F64), n < 2^32, live on one device.  x is  */
+/* a HOST table of C device pointers; it reaches the kernels by value.  */
+/* The definition (sfl_amd/security/aggregation/flame_aggregator.py has */
+/* the host form and the decisions between the two entries):            */
+/*   median  g = the median of the C values of an element, in T: the    */
+/*           middle one for odd C, (lo + hi) / T(2) for even C with the */
+/*           add and the divide each rounded in T (the add may overflow */
+/*           to inf, as numpy's); a NaN among the C gives NaN.  Order:  */
+/*           the total order of the bit patterns, -0 < +0.              */
+/*   stats   C (C + 1) / 2 + C float64:                                 */
+/*             G[i][j] = sum x_i x_j, i <= j, operands converted to     */
+/*                       float64 first, at [i C - i (i - 1) / 2 + j - i]*/
+/*                       (the packed upper triangle, row-major)         */
+/*             N[i]    = sum d_i^2, d_i = x_i - g rounded in T, squared */
+/*                       in float64, at [C (C + 1) / 2 + i]             */
+/*           The order of summation is fixed: a lane's tiles in index   */
+/*           order, a wave's lanes by one butterfly, a block's waves in */
+/*           wave order, the blocks in block order by one block; the    */
+/*           grid is a function of n only.  No atomics: the same input  */
+/*           gives the same bits on every run.                          */
+/*   sa_flame_stats    writes g into median_out (n elements of T) and   */
+/*           this tensor's stats into `stats` (device): added to what   */
+/*           is there when `accumulate`, else stored (agg_flame.py:     */
+/*           61-73 the median, :79-89 and :128-132 the update norms,    */
+/*           :95-112 the cosine distances' Gram matrix).  Layers are    */
+/*           added in call order.  scratch: sa_flame_scratch_bytes      */
+/*           bytes on the device, 8-byte aligned, rewritten by every    */
+/*           call.  n == 0 looks at no pointer but stats and stores     */
+/*           zeros (or adds nothing).  Up to 8 clients one pass over    */
+/*           the tensors; above, two (the Gram matrix's rows split).    */
+/*   sa_flame_combine  out[e] = (sum over the kept clients, in order,   */
+/*           of float64(g + (x_i - g) T(scale_i)) weight_i) / divisor   */
+/*           + 0.0, n float64 on the device (agg_flame.py:141-168 the   */
+/*           clipping, :181-187 np.average, :193-199 the zero-variance  */
+/*           noise term).  The inner expression rounds in T after every */
+/*           operation, the outer multiply and add round separately,    */
+/*           nothing is contracted; the sum starts from +0.0.  scale    */
+/*           and weight are HOST arrays of C doubles.  A client whose   */
+/*           weight is a NaN is dropped: its pointer is not looked at   */
+/*           and its tensor never read.  At least one client is kept.   */
+/* Other element types, n >= 2^32, a client count outside 1 ..          */
+/* SA_FLAME_MAX_CLIENTS, null and misaligned pointers are refused       */
+/* before any launch.  16-byte aligned vectors take 16-byte accesses;   */
+/* others element accesses with the same lane-to-element map.  Nothing  */
+/* may alias an output.  Everything is stream-ordered, allocates        */
+/* nothing and never synchronises with the host.                        */
+/* ------------------------------------------------------------------ */
+#define SA_FLAME_MAX_CLIENTS 16
+
+/* bytes of device scratch sa_flame_stats needs for n elements of n_clients
+ * clients (the blocks' partial sums), or a negative SA_ERR_* code */
+int sa_flame_scratch_bytes(uint64_t n, int n_clients, int x_type);
+
+int sa_flame_stats(const void* const* x, int n_clients, int x_type, uint64_t n, void* median_out, void* scratch,
+                   double* stats, int accumulate, void* stream);
+
+int sa_flame_combine(const void* const* x, const double* scale, const double* weight, int n_clients, int x_type,
+                     uint64_t n, const void* median, double divisor, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

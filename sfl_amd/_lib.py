@@ -28,6 +28,7 @@ SA_COO_BAD_RANGE, SA_COO_BAD_ORDER, SA_COO_BAD_COUNT = 1, 2, 4
 SA_QUANT_ZERO_POINT, SA_QUANT_LSTM = 0, 1
 SA_KMEANS_MAX_K, SA_KMEANS_BINS, SA_KMEANS_BAD_CODE = 256, 4096, 1
 SA_KMEANS_STATE_BYTES, SA_KMEANS_STATE_C, SA_KMEANS_STATE_DONE = 4104, 3072, 4096
+SA_FLAME_MAX_CLIENTS = 16
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -45,6 +46,7 @@ EXPORTED = (
     "sa_quant_scratch_bytes", "sa_quant_range", "sa_quant_affine", "sa_dequant_affine", "sa_quant_fp8",
     "sa_dequant_fp8",
     "sa_kmeans_scratch_bytes", "sa_kmeans_hist", "sa_kmeans_step", "sa_kmeans_labels", "sa_dequant_lut",
+    "sa_flame_scratch_bytes", "sa_flame_stats", "sa_flame_combine",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
 )
 
@@ -167,6 +169,9 @@ def _declare(lib):
     lib.sa_kmeans_step.argtypes = [vp, i32, u64, dbl, dbl, i32, i32, vp, vp]
     lib.sa_kmeans_labels.argtypes = [vp, i32, u64, dbl, dbl, i32, vp, i32, vp, i32, vp]
     lib.sa_dequant_lut.argtypes = [vp, i32, u64, vp, i32, i32, i32, vp, vp, vp]
+    lib.sa_flame_scratch_bytes.argtypes = [u64, i32, i32]
+    lib.sa_flame_stats.argtypes = [P(C.c_void_p), i32, i32, u64, vp, vp, vp, i32, vp]
+    lib.sa_flame_combine.argtypes = [P(C.c_void_p), P(C.c_double), P(C.c_double), i32, i32, u64, vp, dbl, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -1,6 +1,7 @@
 // sa_compress.h — what the compression translation units share (sa_stc.hip,
 // sa_scr.hip, sa_coo.hip, sa_topk.hip, and through sa_runs.h sa_quant.hip and
-// sa_kmeans.hip; nothing else includes it; sa_stc.hip and sa_topk.hip add
+// sa_kmeans.hip; sa_flame.hip, the robust aggregator's passes, takes the wave
+// layout and the entry checks too; nothing else includes it; sa_stc.hip and sa_topk.hip add
 // sa_select.h, the radix select): the block
 // shape, the contiguous wave layout with its launch geometry and the block
 // scan on the device; the element-type dispatch and the first checks of an

@@ -996,3 +996,78 @@ def dequant_lut(q: torch.Tensor, lut: torch.Tensor, offset: int, out: torch.Tens
     L.check(L.lib().sa_dequant_lut(_ptr(q), qb, q.numel(), _ptr(lut), k, int(offset), xt, _ptr(out), _ptr(flag),
                                    C.c_void_p(_stream(out))), "sa_dequant_lut")
     return out
+
+
+# ---------------------------------------------------------------------------
+# FlameAggregator (sa_flame_*; security/aggregation/flame_aggregator.py on top)
+# ---------------------------------------------------------------------------
+def flame_stat_count(n_clients: int) -> int:
+    """The statistics of ``n_clients`` clients: the Gram matrix's packed upper
+    triangle, then the squared update norms."""
+    return n_clients * (n_clients + 1) // 2 + n_clients
+
+
+def flame_scratch_bytes(n: int, n_clients: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``flame_stats`` needs for ``n`` elements of ``n_clients`` clients."""
+    return _scratch_bytes("flame_scratch_bytes", "sa_flame_scratch_bytes", (n, n_clients), dtype)
+
+
+def _flame_table(what: str, xs: Sequence, like: torch.Tensor) -> C.Array:
+    """The host table of the clients' device pointers.  An entry is a tensor
+    of ``like``'s size and dtype, or -- handed to the library as it is, which
+    refuses what it cannot take -- ``None`` or an address."""
+    table = (C.c_void_p * max(1, len(xs)))()
+    for i, x in enumerate(xs):
+        if isinstance(x, torch.Tensor):
+            _require_gpu(x)
+            if x.dtype != like.dtype or x.numel() != like.numel() or not x.is_contiguous() or x.device != like.device:
+                raise ValueError(f"{what}: client {i}'s tensor is contiguous, of the median's size, dtype and device")
+            table[i] = x.data_ptr()
+        else:
+            table[i] = x
+    return table
+
+
+def flame_stats(xs: Sequence, median_out: torch.Tensor, scratch: torch.Tensor, stats: torch.Tensor, *,
+                accumulate: bool = False) -> torch.Tensor:
+    """The element-wise median of the clients' tensors ``xs`` into
+    ``median_out``; their Gram matrix and squared update norms into ``stats``
+    (float64, ``flame_stat_count(len(xs))`` values), added to what is there
+    with ``accumulate``.  The client count, the element type and the pointers
+    are judged by the library.  See sa_flame_stats in include/sfl_sa.h."""
+    _require_gpu(median_out, scratch, stats)
+    c, n = len(xs), median_out.numel()
+    if not median_out.is_contiguous() or not stats.is_contiguous() or stats.dtype != torch.float64:
+        raise ValueError("flame_stats: contiguous tensors; stats is float64")
+    xt = _XTYPE.get(median_out.dtype, -1)
+    if 1 <= c <= L.SA_FLAME_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64):
+        if stats.numel() < flame_stat_count(c):
+            raise ValueError("flame_stats: stats smaller than flame_stat_count(len(xs))")
+        _require_scratch("flame_stats", scratch, flame_scratch_bytes(n, c, median_out.dtype),
+                         "flame_scratch_bytes(n, n_clients, dtype)")
+    table = _flame_table("flame_stats", xs, median_out)
+    L.check(L.lib().sa_flame_stats(table, c, xt, n, _ptr(median_out), _ptr(scratch), _ptr(stats), int(bool(accumulate)),
+                                   C.c_void_p(_stream(median_out))), "sa_flame_stats")
+    return stats
+
+
+def flame_combine(xs: Sequence, scales: Sequence[float], weights: Sequence[float], keep: Sequence[bool],
+                  median: torch.Tensor, divisor: float, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float64) = the weighted average of the kept clients' clipped
+    models ``median + (x - median) * scale``, divided by ``divisor``.  A
+    client with ``keep[i]`` false crosses the C-ABI with a NaN weight, the
+    entry's mark of a dropped client: its tensor is never read.  See
+    sa_flame_combine in include/sfl_sa.h."""
+    _require_gpu(median, out)
+    c, n = len(xs), median.numel()
+    if not (len(scales) == len(weights) == len(keep) == c):
+        raise ValueError("flame_combine: one scale, weight and keep flag per client")
+    if not median.is_contiguous() or not out.is_contiguous() or out.dtype != torch.float64 or out.numel() != n \
+            or out.device != median.device:
+        raise ValueError("flame_combine: out is contiguous float64 of the median's size, on its device")
+    table = _flame_table("flame_combine", xs, median)
+    s = (C.c_double * max(1, c))(*[float(v) for v in scales])
+    w = (C.c_double * max(1, c))(*[float(v) if k else float("nan") for v, k in zip(weights, keep)])
+    L.check(L.lib().sa_flame_combine(table, s, w, c, _XTYPE.get(median.dtype, -1), n, _ptr(median), float(divisor),
+                                     _ptr(out), C.c_void_p(_stream(median))), "sa_flame_combine")
+    return out

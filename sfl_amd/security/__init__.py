@@ -1,1 +1,1 @@
-from .aggregation import Aggregator, SecureAggregator, SparsePlainAggregator  # noqa: F401
+from .aggregation import Aggregator, FlameAggregator, SecureAggregator, SparsePlainAggregator  # noqa: F401
