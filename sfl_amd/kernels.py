@@ -48,8 +48,14 @@ def _require_gpu(*ts):
 
 
 def as_u64(t: torch.Tensor) -> np.ndarray:
-    """Host numpy uint64 view of a uint64-carrying int64 tensor."""
-    return t.detach().cpu().numpy().view(np.uint64)
+    """Host numpy uint64 view of a uint64-carrying int64 tensor: a device
+    tensor is read through a pinned buffer (``hostpipe.d2h``, no pageable
+    DMA), a CPU tensor is viewed in place."""
+    if t.device.type == "cpu":
+        return t.detach().numpy().view(np.uint64)
+    from . import hostpipe as H
+
+    return H.d2h(t, pooled=False).view(np.uint64)
 
 
 def xtype_of(dtype: torch.dtype) -> int:

@@ -13,7 +13,13 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from gpu_copies import _host
 from oracle import secagg as o
+
+
+def _np(t):
+    """A window on the host: a CPU tensor as it is, a device tensor through a pinned buffer."""
+    return t.numpy() if t.device.type == "cpu" else _host(t)
 
 
 def window_starts(n: int, w: int, joins=(), k_random: int = 5, seed: int = 0) -> list[int]:
@@ -37,12 +43,12 @@ def check_partial_sum_windows(out: torch.Tensor, xs, clients, names, seeds, offs
     checked = 0
     for s0 in window_starts(n, w, joins, k_random, seed):
         e = min(n, s0 + w)
-        xh = [xs[c][s0:e].cpu().numpy() for c in clients]
+        xh = [_np(xs[c][s0:e]) for c in clients]
         exp = np.zeros(e - s0, dtype=np.uint64)
         for c, x in zip(clients, xh):
             me = names[c]
             exp += o.mask_client(o.quantize(x), me, seeds[me], offset + s0)
-        got = out[s0:e].cpu().numpy().view(np.uint64)
+        got = _np(out[s0:e]).view(np.uint64)
         bad = np.flatnonzero(got != exp)
         assert bad.size == 0, f"window [{s0}, {e}): {bad.size} elements differ, first at {s0 + int(bad[0])}"
         checked += e - s0

@@ -12,6 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 from torch import nn  # noqa: E402
 
+from gpu_copies import _host  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 from test_fl_round import NAMES, MlpNet, OracleAggregator, _data  # noqa: E402
 
@@ -208,7 +209,7 @@ def test_gpu_model_keeps_everything_on_the_device():
         assert all(np.array_equal(a, b) for a, b in zip(before, w.get_weights()))
         for sparse, res, old in zip(payload, w._res, w.model_weights):
             assert sparse.is_cuda and res.is_cuda and old.is_cuda and sparse.dtype == torch.float32
-            assert _is_ternary(sparse.cpu().numpy(), sparse.numel() - round(0.9 * sparse.numel()))
+            assert _is_ternary(_host(sparse), sparse.numel() - round(0.9 * sparse.numel()))
     seeds = o.seeds_for(NAMES)
     pair = {(a, b): seeds[a][b] for a in NAMES for b in NAMES if a != b}
     pyus = [PYU(n, 0) for n in NAMES]
@@ -217,10 +218,10 @@ def test_gpu_model_keeps_everything_on_the_device():
                    train_device=None, hook=lambda r, p: down.append(p))
     for t in down[-1]:
         assert t.is_cuda and t.dtype == torch.float64
-        assert _is_ternary(t.cpu().numpy(), t.numel() - round(0.5 * t.numel()))
+        assert _is_ternary(_host(t), t.numel() - round(0.5 * t.numel()))
     assert all(s.is_cuda and s.dtype == torch.float64 for s in fl.server_weight)
     w0 = fl.get_weights(pyus[0])
     for p in pyus[1:]:
         assert all(np.array_equal(a, b) for a, b in zip(w0, fl.get_weights(p)))
     for a, s in zip(w0, fl.server_weight):
-        assert np.allclose(a, s.cpu().numpy(), rtol=0, atol=1e-5)
+        assert np.allclose(a, _host(s), rtol=0, atol=1e-5)

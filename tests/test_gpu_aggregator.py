@@ -14,6 +14,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -180,7 +181,7 @@ def test_rounds_match_oracle_bit_exact(fused, keep):
             assert np.array_equal(got[li], exp.reshape(xs[0].shape)), (rnd, li)
             if keep:
                 for c in range(len(names)):
-                    assert np.array_equal(agg.last_masked[li][c].cpu().numpy().view(np.uint64), masked[c].reshape(-1))
+                    assert np.array_equal(_u64(agg.last_masked[li][c]), masked[c].reshape(-1))
             offset += xs[0].size
         if keep:
             assert len(agg.last_masked) == 2
@@ -197,7 +198,7 @@ def test_torch_payload_stays_on_device():
     ts = [torch.randn(1000, device="cuda:0") for _ in ps]
     out = rv(agg.sum([p(lambda t=t: t)() for p, t in zip(ps, ts)], axis=0))
     assert isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
-    assert float((out - torch.stack(ts).double().sum(0)).abs().max()) < 3 * 2.0**-18
+    assert float(_item((out - torch.stack(ts).double().sum(0)).abs().max())) < 3 * 2.0**-18
 
 
 def test_single_participant_and_errors():
@@ -351,9 +352,9 @@ def test_many_colocated_parties_pair_shared(as_torch):
     for rnd in range(3):
         xs = [(rng.standard_normal(1001) * 0.1).astype(np.float32) for _ in names]
         w = [3 * c + rnd + 1 for c in range(C)]
-        objs = [p(lambda x=x: torch.from_numpy(x).cuda() if as_torch else x)() for p, x in zip(pyus, xs)]
+        objs = [p(lambda x=x: _dev(x) if as_torch else x)() for p, x in zip(pyus, xs)]
         got = rv(agg.average(objs, axis=0, weights=w))
-        got = got.cpu().numpy() if as_torch else got
+        got = _host(got) if as_torch else got
         exp = o.secure_average(xs, names, weights=w, seeds=seeds, offset=offset)[0]
         assert np.array_equal(got, exp), rnd
         offset += xs[0].size
@@ -497,7 +498,7 @@ def test_general_one_call_matches_general_path(dtype, monkeypatch):
         outs = []
         for data in rounds:
             got = rv(agg.average([p(lambda d=d: d)() for p, d in zip(pyus, data)], axis=0, weights=weights))
-            digs = [np.asarray(d.cpu() if hasattr(d, "cpu") else d).view(np.uint64).copy()
+            digs = [np.asarray(_host(d) if hasattr(d, "cpu") else d).view(np.uint64).copy()
                     for d in agg.last_digests if d is not None]
             outs.append((got, digs))
         pos = {nm: {p: agg._maskers[nm].position(p) for p in names if p != nm} for nm in names}

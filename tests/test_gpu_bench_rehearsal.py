@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _host  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,7 +52,7 @@ def oracle_check(C: int, n: int, fxp_bits: int = 18) -> str:
     s = np.zeros(n, dtype=np.uint64)
     for c in range(C):  # accumulated client by client (no C x n stack at 100M)
         g = torch.Generator(device=dev).manual_seed(20260116 + c)
-        x = (torch.randn(n, generator=g, device=dev, dtype=torch.float32) * 1e-2).cpu().numpy()
+        x = _host(torch.randn(n, generator=g, device=dev, dtype=torch.float32) * 1e-2)
         s += o.quantize(x, None, fxp_bits)
         del x
     dec = o.decode(s, fxp_bits)

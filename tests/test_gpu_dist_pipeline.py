@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -86,15 +88,15 @@ def _worker(rank, world, init, n, chunks, offset, kind, q):
         part = torch.empty(n, dtype=torch.int64, device=dev)
         dig = torch.zeros(len(plan.clients), dtype=torch.int64, device=dev)
         flags = torch.zeros(1, dtype=torch.int32, device=dev)
-        pipe.run([torch.from_numpy(xs[c]).to(dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
+        pipe.run([_dev(xs[c], device=dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
                  plan.n_cross, part, None, digests=dig, flags=flags)
         torch.cuda.synchronize()
         masked = o.secure_masked(xs, names, seeds=seeds, offset=offset)
-        dig_ok = [int(d) for d in dig.cpu().numpy().view(np.uint64)] == [o.digest(masked[c]) for c in plan.clients]
+        dig_ok = [int(d) for d in _u64(dig)] == [o.digest(masked[c]) for c in plan.clients]
         sum_ok = True
         if rank == 0:
-            sum_ok = bool(np.array_equal(part.cpu().numpy().view(np.uint64), o.server_sum(masked)))
-        q.put((rank, dig_ok, sum_ok, int(flags.item())))
+            sum_ok = bool(np.array_equal(_u64(part), o.server_sum(masked)))
+        q.put((rank, dig_ok, sum_ok, int(_item(flags))))
         dist.destroy_process_group()
     except BaseException as e:  # noqa: BLE001 - reported to the parent
         q.put((rank, repr(e), False, -1))
@@ -133,12 +135,12 @@ def _worker_sharded(rank, world, init, n, chunks, offset, exchange, kind, q):
         gens = [plan_generators(plan, seed_of, offset=offset + lo) for lo, _ in pipe.bounds]
         part = torch.zeros(pipe.buffer_len, dtype=torch.int64, device=dev)
         dec = torch.zeros(pipe.buffer_len, dtype=torch.float64, device=dev)
-        pipe.run([torch.from_numpy(xs[c]).to(dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
+        pipe.run([_dev(xs[c], device=dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
                  plan.n_cross, part, None, dec=dec, gather=True)
         torch.cuda.synchronize()
         ssum = o.server_sum(o.secure_masked(xs, names, seeds=seeds, offset=offset))
         want = o.decode(ssum)
-        got_s, got_d = part.cpu().numpy().view(np.uint64), dec.cpu().numpy()
+        got_s, got_d = _u64(part), _host(dec)
         shard_ok = all(np.array_equal(got_s[a:b], ssum[a:b]) and np.array_equal(got_d[a:b], want[a:b])
                        for a, b in rank_shards(pipe.bounds, world, rank, n))
         full_ok = bool(np.array_equal(got_d[:n], want)) if rank == 0 else True

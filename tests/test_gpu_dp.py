@@ -5,11 +5,11 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import DEV, _dev, _host, _item, _u64  # noqa: E402
 from oracle import dp as D  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,16 +42,16 @@ def test_sumsq_deterministic_and_accurate(n):
     a, b = _sumsq(x), _sumsq(x)
     torch.cuda.synchronize()
     assert torch.equal(a, b)
-    xh = x.cpu().numpy()
-    assert a.item() == float(D.layer_sq_norm(xh))
-    nrm = np.sqrt(a.item())
-    assert np.float32(nrm) == nrm and nrm * nrm == a.item()  # the exact square of a float32 norm
+    xh = _host(x)
+    assert _item(a) == float(D.layer_sq_norm(xh))
+    nrm = np.sqrt(_item(a))
+    assert np.float32(nrm) == nrm and nrm * nrm == _item(a)  # the exact square of a float32 norm
     from sfl_amd import _lib as L
 
     part = torch.empty(L.SA_DP_PARTIALS, dtype=torch.float64, device=DEV)
     y = torch.randn(n + 5, device=DEV)
     _K().sumsq_f32(y, a, part, accumulate=True)
-    assert a.item() == float(D.global_sq([xh, y.cpu().numpy()]))
+    assert _item(a) == float(D.global_sq([xh, _host(y)]))
 
 
 # k_sumsq_partial's grid is capped at 1,024 blocks x 256 lanes x one float4:
@@ -77,25 +77,25 @@ def test_sumsq_multi_trip_exact(n):
       squared, 17.999999..., as D.layer_sq_norm forms it), and 3.0 with 4.0:
       exactly 25.0."""
     x = torch.ones(n, device=DEV)
-    got = _sumsq(x).item()
+    got = _item(_sumsq(x))
     assert got == float(np.float32(np.sqrt(np.float32(n)))) ** 2
     assert got == float(D.layer_sq_norm(np.ones(n, dtype=np.float32)))
     x.zero_()
-    assert _sumsq(x).item() == 0.0
+    assert _item(_sumsq(x)) == 0.0
     pos = sorted({p for p in (0, 4 * (n // 4) - 1, n - 1, GRID_ELEMS - 1, GRID_ELEMS, 2 * GRID_ELEMS - 1,
                               2 * GRID_ELEMS) if 0 <= p < n})
     for p in pos:
         x[p] = 3.0
-        assert _sumsq(x).item() == 9.0, p
+        assert _item(_sumsq(x)) == 9.0, p
         x[p] = 0.0
     two = float(np.float32(np.sqrt(np.float32(18.0)))) ** 2
     assert two == float(D.layer_sq_norm(np.array([3.0, 3.0], dtype=np.float32))) and abs(two - 18.0) < 18 * 2.0**-22
     for p, q in list(zip(pos, pos[1:])) + [(pos[0], pos[-1])]:
         x[p] = 3.0
         x[q] = 3.0
-        assert _sumsq(x).item() == two, (p, q)
+        assert _item(_sumsq(x)) == two, (p, q)
         x[q] = 4.0
-        assert _sumsq(x).item() == 25.0, (p, q)
+        assert _item(_sumsq(x)) == 25.0, (p, q)
         x[p] = 0.0
         x[q] = 0.0
 
@@ -111,13 +111,13 @@ def test_sumsq_multi_trip_random(n):
     a, b = _sumsq(x), _sumsq(x)
     torch.cuda.synchronize()
     assert torch.equal(a, b)
-    xh = x.cpu().numpy()
-    assert a.item() == float(D.layer_sq_norm(xh))
+    xh = _host(x)
+    assert _item(a) == float(D.layer_sq_norm(xh))
     part = torch.empty(L.SA_DP_PARTIALS, dtype=torch.float64, device=DEV)
     y = x[: 2 * GRID_ELEMS + 4 * 77 + 1] * 0.5 if n > 3 * GRID_ELEMS else x[4: n - 1] * 0.5
     assert y.data_ptr() % 16 == 0
     _K().sumsq_f32(y, a, part, accumulate=True)
-    assert a.item() == float(D.global_sq([xh, y.cpu().numpy()]))
+    assert _item(a) == float(D.global_sq([xh, _host(y)]))
 
 
 def _edge_inputs(n):
@@ -149,35 +149,35 @@ def test_clip_edges_vs_oracle(case, each_layer):
 
     n, clip, key, ctr = 4099, 0.5, 0xC0FFEE, 4 * 9
     xh = _edge_inputs(n)[case]
-    x = torch.from_numpy(xh).to(DEV)
+    x = _dev(xh)
     with np.errstate(all="ignore"):
         want_sq = D.layer_sq_norm(xh)
     layer = _sumsq(x)
-    assert np.array_equal(layer.cpu().numpy(), np.array([want_sq]), equal_nan=True), (layer.item(), want_sq)
+    assert np.array_equal(_host(layer), np.array([want_sq]), equal_nan=True), (_item(layer), want_sq)
     if case == "all zeros":
-        assert layer.item() == 0.0
+        assert _item(layer) == 0.0
     elif case in ("dot above float32's range", "one inf"):
-        assert layer.item() == np.inf
+        assert _item(layer) == np.inf
     elif case == "one NaN":
-        assert np.isnan(layer.item())
+        assert np.isnan(_item(layer))
     else:
-        assert abs(layer.item() / 1e36 - 1) < 1e-6  # finite: float32 holds the dot, float64 the partial sums
+        assert abs(_item(layer) / 1e36 - 1) < 1e-6  # finite: float32 holds the dot, float64 the partial sums
     total, other = layer, np.full(100, 1.5, dtype=np.float32)
     if each_layer:
         total = layer.clone()
         part = torch.empty(L.SA_DP_PARTIALS, dtype=torch.float64, device=DEV)
-        K.sumsq_f32(torch.from_numpy(other).to(DEV), total, part, accumulate=True)
+        K.sumsq_f32(_dev(other), total, part, accumulate=True)
         with np.errstate(all="ignore"):
             want_total = D.global_sq([xh, other])
-        assert np.array_equal(total.cpu().numpy(), np.array([want_total]), equal_nan=True)
+        assert np.array_equal(_host(total), np.array([want_total]), equal_nan=True)
     with np.errstate(all="ignore"):
-        scale = D.clip_scale(total.item(), clip, layer.item() if each_layer else None)
+        scale = D.clip_scale(_item(total), clip, _item(layer) if each_layer else None)
     assert scale == {"one 1e18 among 1e-3": scale, "all zeros": 1.0, "dot above float32's range": 0.0, "one NaN": 1.0,
                      "one inf": 0.0}[case]
     assert 0.0 <= scale <= 1.0
     kw = dict(l2_norm_clip=clip, key=key, counter0=ctr, sumsq_layer=layer if each_layer else None)
     # without noise: x * scale exactly
-    y0 = K.dp_perturb(x, torch.empty_like(x), K.make_dp(total, noise_std=0.0, num_updates=4, **kw)).cpu().numpy()
+    y0 = _host(K.dp_perturb(x, torch.empty_like(x), K.make_dp(total, noise_std=0.0, num_updates=4, **kw)))
     with np.errstate(all="ignore"):
         exp0 = D.perturb(xh, scale, np.zeros(n, np.float32), 0.0, 4)
     assert np.array_equal(y0, exp0, equal_nan=True)
@@ -186,7 +186,7 @@ def test_clip_edges_vs_oracle(case, each_layer):
     # with noise
     for updates in (4, 3):
         y = K.dp_perturb(x, torch.empty_like(x), K.make_dp(total, noise_std=0.3, num_updates=updates, **kw))
-        y = y.cpu().numpy()
+        y = _host(y)
         with np.errstate(all="ignore"):
             exp = D.perturb(xh, scale, D.gauss(key, ctr, n), 0.3, updates)
         assert np.allclose(y, exp, rtol=2e-5, atol=2e-6, equal_nan=True)
@@ -195,7 +195,7 @@ def test_clip_edges_vs_oracle(case, each_layer):
             s1 = _sumsq(torch.ones(4, device=DEV))
             z = K.dp_perturb(x, torch.empty_like(x), K.make_dp(s1, l2_norm_clip=clip, noise_std=0.3,
                                                                 num_updates=updates, key=key, counter0=ctr))
-            assert np.array_equal(y.view(np.uint32), z.cpu().numpy().view(np.uint32))
+            assert np.array_equal(y.view(np.uint32), _host(z).view(np.uint32))
             # the normal's tolerance scaled by sigma / updates, plus the two float32 roundings
             f = np.float64(np.float32(0.3)) / updates
             z64 = D.gauss64(key, ctr, n)
@@ -211,8 +211,8 @@ def test_perturb_clip_exact_without_noise(clip):
     dp = K.make_dp(s, l2_norm_clip=clip, noise_std=0.0, num_updates=4, key=1)
     y = K.dp_perturb(x, torch.empty_like(x), dp)
     torch.cuda.synchronize()
-    scale = D.clip_scale(s.item(), clip)
-    assert np.array_equal(y.cpu().numpy(), x.cpu().numpy() * scale)
+    scale = D.clip_scale(_item(s), clip)
+    assert np.array_equal(_host(y), _host(x) * scale)
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 1024, 1025, 4095, 4096, 4097, 262_147])
@@ -229,9 +229,9 @@ def test_perturb_tile_edges_and_no_write_past_n(n):
     K.dp_perturb(x, buf[:n], dp)
     torch.cuda.synchronize()
     assert torch.all(buf[n:] == 12345.0)
-    xh = x.cpu().numpy()
-    exp = D.perturb(xh, D.clip_scale(s.item(), 0.5), D.gauss(key, ctr, n), 0.3, 4)
-    assert np.allclose(buf[:n].cpu().numpy(), exp, rtol=2e-5, atol=2e-6)
+    xh = _host(x)
+    exp = D.perturb(xh, D.clip_scale(_item(s), 0.5), D.gauss(key, ctr, n), 0.3, 4)
+    assert np.allclose(_host(buf[:n]), exp, rtol=2e-5, atol=2e-6)
 
 
 @pytest.mark.parametrize("updates", [4, 3])
@@ -241,7 +241,7 @@ def test_perturb_noise_matches_oracle_stream(updates):
     x = torch.zeros(n, device=DEV)
     s = _sumsq(torch.ones(4, device=DEV))
     dp = K.make_dp(s, l2_norm_clip=1.0, noise_std=1.5, num_updates=updates, key=key, counter0=ctr)
-    y = K.dp_perturb(x, torch.empty_like(x), dp).cpu().numpy()
+    y = _host(K.dp_perturb(x, torch.empty_like(x), dp))
     z = D.gauss(key, ctr, n)
     exp = D.perturb(np.zeros(n, np.float32), 1.0, z, 1.5, updates)
     assert np.allclose(y, exp, rtol=2e-5, atol=2e-6)
@@ -269,14 +269,14 @@ def test_fused_mask_dp_equals_perturb_then_mask(nstreams, updates):
     K.mask_dp(x, m2, streams, mk(), weight=3.0, digest=d2)
     torch.cuda.synchronize()
     bad = (m1 != m2).nonzero().flatten()
-    assert bad.numel() == 0, f"{bad.numel()} masked elements differ, first {bad[:8].tolist()}"
+    assert bad.numel() == 0, f"{bad.numel()} masked elements differ, first {_host(bad[:8]).tolist()}"
     assert torch.equal(d1, d2)
     # and the masked vector is the oracle's for the perturbed input
-    exp = o.quantize(xp.cpu().numpy(), 3)
+    exp = o.quantize(_host(xp), 3)
     for sd, (_, sg, _) in zip(seeds, streams):
         mm = o.mask_stream(sd, n)
         exp = exp + mm if sg > 0 else exp - mm
-    assert np.array_equal(m2.cpu().numpy().view(np.uint64), exp)
+    assert np.array_equal(_u64(m2), exp)
 
 
 @pytest.mark.parametrize("each_layer", [False, True])
@@ -330,15 +330,15 @@ def test_gaussian_model_dp_called_twice_advances_the_noise(each_layer):
         if g1.size:
             assert np.mean(g1 != g2) > 0.99 and g1.reshape(-1)[0] != g2.reshape(-1)[0]
     dpt = mk()
-    tin = [torch.from_numpy(a).to(DEV) for a in layers]
+    tin = [_dev(a).reshape(a.shape) for a in layers]
     for got in calls:
         tout = dpt(tin)
         for t, g in zip(tout, got):
             assert isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and tuple(t.shape) == g.shape
-            assert np.array_equal(t.cpu().numpy().view(np.uint32), g.view(np.uint32))
+            assert np.array_equal(_host(t).view(np.uint32), g.view(np.uint32))
     assert dpt.counter == 2 * step
     for t, a in zip(tin, layers):  # the inputs are left alone
-        assert np.array_equal(t.cpu().numpy(), a)
+        assert np.array_equal(_host(t), a)
 
 
 def _reference_clip_numpy(inputs, clip, each_layer):
@@ -441,8 +441,8 @@ def test_loopback_client_dp_round_vs_oracle():
     for r in range(rounds):
         xp = []
         for dp, x in zip(dps, xs):
-            d = torch.from_numpy(x).to(DEV)
-            xp.append(K.dp_perturb(d, torch.empty_like(d), dp.params(dp.sumsq([d]), n)).cpu().numpy())
+            d = _dev(x)
+            xp.append(_host(K.dp_perturb(d, torch.empty_like(d), dp.params(dp.sumsq([d]), n))))
         exp = o.secure_sum(xp, names, seeds=seeds, offset=r * n)[0]
         assert np.array_equal(got[r], exp), r
         for i in range(len(names)):
@@ -457,7 +457,7 @@ def test_loopback_client_dp_round_vs_oracle():
         # round 2's noise is the stream's next window, not round 1's (the inputs are the same)
         assert np.mean(xps[0][i] != xps[1][i]) > 0.99
         z2 = D.gauss(100 + i, n4, n)
-        exp2 = D.perturb(xs[i], D.clip_scale(dp.sumsq([torch.from_numpy(xs[i]).to(DEV)]).item(), 0.8), z2,
+        exp2 = D.perturb(xs[i], D.clip_scale(_item(dp.sumsq([_dev(xs[i])])), 0.8), z2,
                          0.5 * 0.8 * 0.8, 3)
         assert np.allclose(xps[1][i], exp2, rtol=2e-5, atol=2e-6)
     assert np.mean(exps[0] != exps[1]) > 0.99

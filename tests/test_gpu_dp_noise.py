@@ -12,11 +12,11 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import dp_noise_stats as S  # noqa: E402
+from gpu_copies import DEV, _dev, _host, _item, _u64  # noqa: E402
 from oracle import dp as D  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SENTINEL = 12345.0
 
 
@@ -52,7 +52,7 @@ def _normals(key, counter0, n):
     dp = K.make_dp(s, l2_norm_clip=1.0, noise_std=1.0, num_updates=1, key=key, counter0=counter0)
     y = K.dp_perturb(torch.zeros(n, device=DEV), torch.full((n,), SENTINEL, device=DEV), dp)
     torch.cuda.synchronize()
-    return y.cpu().numpy()
+    return _host(y)
 
 
 def _streams(nstreams):
@@ -118,15 +118,15 @@ def _fused_vs_perturb_then_mask(x, key, counter0, updates, nstreams=3, noise_std
     K.mask_dp(x, m2, streams, mk(), weight=3.0, digest=d2)
     torch.cuda.synchronize()
     bad = (m1 != m2).nonzero().flatten()
-    assert bad.numel() == 0, f"{bad.numel()} masked elements differ, first {bad[:8].tolist()}"
+    assert bad.numel() == 0, f"{bad.numel()} masked elements differ, first {_host(bad[:8]).tolist()}"
     assert torch.equal(d1, d2)
-    xph = xp.cpu().numpy()
+    xph = _host(xp)
     exp = o.quantize(xph, 3)
     for sd, (_, sg, _) in zip(seeds, streams):
         mm = o.mask_stream(sd, n)
         exp = exp + mm if sg > 0 else exp - mm
-    assert np.array_equal(m2.cpu().numpy().view(np.uint64), exp)
-    return xph, D.clip_scale(s.item(), 0.3)
+    assert np.array_equal(_u64(m2), exp)
+    return xph, D.clip_scale(_item(s), 0.3)
 
 
 def _fused_normals(key, counter0, n):
@@ -139,7 +139,7 @@ def _fused_normals(key, counter0, n):
     m = torch.empty(n, dtype=torch.int64, device=DEV)
     K.mask_dp(torch.zeros(n, device=DEV), m, [], dp, weight=1.0, fxp_bits=40)
     torch.cuda.synchronize()
-    return m.cpu().numpy()
+    return _host(m)
 
 
 EXTREME_IDS = [f"{e[0].split(' (')[0]} @ {e[1]}".replace(" ", "") for e in S.EXTREMES]
@@ -170,11 +170,11 @@ def test_extreme_inputs_fused_equals_perturb_then_mask(updates):
     kernel's."""
     for name, blk, j, which, val in S.EXTREMES:
         c0 = 4 * (blk - 1)
-        x = torch.tensor([0.01, -0.02, 0.03, 0.005, -0.015, 0.025, 0.02, -0.01, 0.004, -0.03, 0.011, 0.007],
-                         device=DEV)
+        x = _dev(np.array([0.01, -0.02, 0.03, 0.005, -0.015, 0.025, 0.02, -0.01, 0.004, -0.03, 0.011, 0.007],
+                          np.float32))
         xp, scale = _fused_vs_perturb_then_mask(x, S.KEY, c0, updates)
         z64 = D.gauss64(S.KEY, c0, 12)
-        noise = (xp.astype(np.float64) - (x.cpu().numpy() * scale).astype(np.float64)) * updates
+        noise = (xp.astype(np.float64) - (_host(x) * scale).astype(np.float64)) * updates
         # x * scale + z / updates in float32: two roundings of values below 8 on top of the normal's tolerance
         assert np.all(np.abs(noise - z64) <= S.RTOL * np.abs(z64) + S.ATOL + updates * 8 * 2.0**-23), (name, blk)
         zs = _normals(S.KEY, c0, 12)

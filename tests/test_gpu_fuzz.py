@@ -14,6 +14,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -87,7 +88,7 @@ def test_plugin_random_cases_match_oracle(seed):
             w = None
         objs = []
         for p, d in zip(pyus, data):
-            payload = [torch.from_numpy(a).to("cuda:0") for a in d] if as_torch else d
+            payload = [_dev(a).reshape(a.shape) for a in d] if as_torch else d
             objs.append(p(lambda x=payload: x)())
         if wkind == "vec":
             # per-element weights only for single-array payloads (np.average semantics)
@@ -107,12 +108,12 @@ def test_plugin_random_cases_match_oracle(seed):
                 exp, s, masked = o.secure_average(xs, names, weights=w, seeds=seeds, offset=offset)
             else:
                 exp, s, masked = o.secure_sum(xs, names, seeds=seeds, offset=offset)
-            g = got[li].cpu().numpy() if as_torch else got[li]
+            g = _host(got[li]) if as_torch else got[li]
             assert g.dtype == np.float64 and g.shape == sh, (seed, rnd, li)
             assert np.array_equal(g.reshape(-1), exp.reshape(-1)), (seed, rnd, li, mode, dts[li], wkind)
             if mode == "keep" and sh[0] != 0:
                 for c in range(C):
-                    mv = agg.last_masked[li][c].cpu().numpy().view(np.uint64)
+                    mv = _u64(agg.last_masked[li][c])
                     assert np.array_equal(mv, masked[c].reshape(-1)), (seed, rnd, li, c)
             offset += int(np.prod(sh))
 
@@ -163,11 +164,11 @@ def test_fused_launch_random_shapes_match_oracle(seed):
                           1 if names[v] > names[u] else -1, v))
     want_dig, want_mo, acc = (bool(rng.random() < 0.5) for _ in range(3))
     base = rng.integers(0, 2**63, n).astype(np.uint64) if acc else np.zeros(n, np.uint64)
-    s = torch.from_numpy(base.view(np.int64).copy()).to("cuda:0")
+    s = _dev(base.view(np.int64).copy())
     dig = torch.zeros(Lc, dtype=torch.int64, device="cuda:0") if want_dig else None
     mo = [torch.empty(n, dtype=torch.int64, device="cuda:0") for _ in local] if want_mo else None
     flags = torch.zeros(1, dtype=torch.int32, device="cuda:0")
-    K.fused_clients([torch.from_numpy(xs[u]).to("cuda:0") for u in local], [ws[u] for u in local], pg, ps,
+    K.fused_clients([_dev(xs[u]) for u in local], [ws[u] for u in local], pg, ps,
                     cross, len(remote), s, accumulate=acc, digests=dig, flags=flags, masked_outs=mo)
     torch.cuda.synchronize()
     exp = base.copy()
@@ -180,7 +181,7 @@ def test_fused_launch_random_shapes_match_oracle(seed):
             assert np.array_equal(K.as_u64(mo[u]), masked[u]), ctx + (u,)
     if want_dig:
         assert [int(v) for v in K.as_u64(dig)] == [o.digest(masked[u]) for u in local], ctx
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 N_MANY_CASES = 24
@@ -211,10 +212,10 @@ def test_many_clients_random_cases_match_oracle(seed):
             ps.append(1 if names[v] > names[u] else -1)
     exp = o.server_sum(o.secure_masked(xs, names, weights=w, seeds=seeds, offset=offset))
     dev = torch.device("cuda", 0)
-    xt = [torch.from_numpy(x).to(dev) for x in xs]
+    xt = [_dev(x, device=dev) for x in xs]
     accumulate = bool(rng.integers(0, 2))
     base = rng.integers(0, 2**64 - 1, n, dtype=np.uint64) if accumulate else np.zeros(n, dtype=np.uint64)
-    s = torch.from_numpy(base.view(np.int64).copy()).to(dev)
+    s = _dev(base.view(np.int64).copy(), device=dev)
     K.fused_many(xt, [float(v) for v in w], pg, ps, s, accumulate=accumulate)
     s2 = torch.empty(n, dtype=torch.int64, device=dev)
     K.fused_clients(xt, [float(v) for v in w], pg, ps, [], 0, s2, digests=torch.zeros(C, dtype=torch.int64, device=dev))

@@ -14,9 +14,9 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-pytestmark = pytest.mark.gpu
+from gpu_copies import DEV, _dev, _item  # noqa: E402
 
-DEV = "cuda:0"
+pytestmark = pytest.mark.gpu
 T = 512  # elements per tile
 NAMES8 = ["p3", "p0", "p6", "p1", "p7", "p2", "p5", "p4"]  # mixed order: both pair signs occur
 N8 = 300_001  # grid 512, 586 tiles: 74 blocks take the tile jump a second time
@@ -55,7 +55,7 @@ def eight():
     total = o.server_sum(masked)
     total.setflags(write=False)
     pg, ps = _gens(NAMES8, seeds)
-    return {"xs": xs, "xt": [torch.from_numpy(x).to(DEV) for x in xs], "masked": masked, "sum": total,
+    return {"xs": xs, "xt": [_dev(x) for x in xs], "masked": masked, "sum": total,
             "pg": pg, "ps": ps}
 
 
@@ -68,7 +68,7 @@ def test_eight_clients_sum_only(eight, n):
     K.fused_clients([x[:n] for x in eight["xt"]], [1.0] * 8, eight["pg"], eight["ps"], [], 0, s, flags=flags)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(s), eight["sum"][:n])
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 @pytest.mark.parametrize("n", SIZES8)
@@ -118,7 +118,7 @@ def _rank_case(C, W, r, n, offset, seed):
     exp = np.zeros(n, dtype=np.uint64)
     for c in plan.clients:
         exp += o.mask_client(o.quantize(xs[c]), names[c], seeds[names[c]], offset)
-    return plan, [torch.from_numpy(xs[c]).to(DEV) for c in plan.clients], pg, ps, cross, exp
+    return plan, [_dev(xs[c]) for c in plan.clients], pg, ps, cross, exp
 
 
 # per-rank shapes of 8 clients: <4,4> (W = 2), <2,6> (W = 4), the lean <1,7> (W = 8); the long sizes go past
@@ -135,7 +135,7 @@ def test_per_rank_shapes(W, n):
     K.fused_clients(xt, [1.0] * len(xt), pg, ps, cross, plan.n_cross, s, flags=flags)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(s), exp)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 def test_multi_launch_schedule_stored_and_accumulated():
@@ -149,7 +149,7 @@ def test_multi_launch_schedule_stored_and_accumulated():
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     K.fused_clients(xt, [1.0] * 4, pg, ps, cross, plan.n_cross, s)
     init = np.random.default_rng(5).integers(0, 2**63, n, dtype=np.int64)
-    acc = torch.from_numpy(init).to(DEV)
+    acc = _dev(init)
     K.fused_clients(xt, [1.0] * 4, pg, ps, cross, plan.n_cross, acc, accumulate=True)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(s), exp)
@@ -171,7 +171,7 @@ def test_sixteen_colocated_clients_bipartite_blocks():
     pg, ps = _gens(names, seeds)
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
-    K.fused_clients([torch.from_numpy(x).to(DEV) for x in xs], [1.0] * C, pg, ps, [], 0, s, flags=flags)
+    K.fused_clients([_dev(x) for x in xs], [1.0] * C, pg, ps, [], 0, s, flags=flags)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(s), exp)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0

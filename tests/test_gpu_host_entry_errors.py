@@ -26,10 +26,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import DEV, _dev, _host, _item  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 N = 2_000_003  # ~8-16 MB per copy: a copy still in flight at return would be seen by query()
 
 
@@ -278,13 +278,13 @@ def test_sum_f64_chain_adds_strictly_left_to_right(k, n, shift):
     wb = []
     for w in ws:
         b = torch.empty(n + 1, dtype=torch.float64, device=DEV)
-        b[shift:shift + n] = torch.from_numpy(w).to(DEV)
+        b[shift:shift + n] = _dev(w)
         wb.append(b[shift:shift + n])
     ob = torch.full((n + 1,), float("nan"), dtype=torch.float64, device=DEV)
     got = K.sum_f64(wb, ob[shift:shift + n])
     torch.cuda.synchronize()
-    assert np.array_equal(got.cpu().numpy(), functools.reduce(np.add, ws))
-    assert np.isnan(ob[n if shift == 0 else 0].item())  # nothing written past the vector
+    assert np.array_equal(_host(got), functools.reduce(np.add, ws))
+    assert np.isnan(_item(ob[n if shift == 0 else 0]))  # nothing written past the vector
 
 
 @pytest.mark.parametrize("k", [2, 33])
@@ -294,7 +294,7 @@ def test_sum_u64_out_may_alias_its_first_input(k):
     n = 4099
     rng = np.random.default_rng(k)
     host = [rng.integers(0, 2**64 - 1, n, dtype=np.uint64) for _ in range(k)]
-    ins = [torch.from_numpy(h.view(np.int64)).to(DEV) for h in host]
+    ins = [_dev(h.view(np.int64)) for h in host]
     got = K.sum_u64(ins, ins[0])
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(got), o.server_sum(host))

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -61,21 +62,21 @@ def test_d2h_h2d_views_tensors_and_u64(monkeypatch):
     dev = torch.device("cuda", 0)
     base = torch.arange(4_000_000, dtype=torch.int64, device=dev).reshape(2000, 2000)
     view = base.t()[::2]  # non-contiguous device view
-    assert np.array_equal(H.d2h(view), view.cpu().numpy())
+    assert np.array_equal(H.d2h(view), np.arange(4_000_000, dtype=np.int64).reshape(2000, 2000).T[::2])
     # uint64 host arrays (masked vectors) go up as their int64 bits
     u = np.arange(2**64 - 1000, 2**64 - 1, dtype=np.uint64)
     t = H.h2d(u, dev)
     assert t.dtype == torch.int64 and np.array_equal(H.d2h(t).view(np.uint64), u)
     # a CPU tensor is a host array; a device tensor is moved as it is
     x = torch.randn(300_001)
-    assert torch.equal(H.h2d(x, dev).cpu(), x)
+    assert np.array_equal(H.d2h(H.h2d(x, dev), pooled=False), x.numpy())
     y = torch.randn(10, device=dev)
     assert H.h2d(y, dev).data_ptr() == y.data_ptr()
     # an array inside a pooled result is copied as it is (already registered)
     owner = H.RESULTS.take(16 << 20)
     pooled = owner[: 8 << 20].view(np.float64)
     pooled[:] = np.arange(pooled.size)
-    assert torch.equal(H.h2d(pooled[5:], dev).cpu(), torch.from_numpy(pooled[5:]))
+    assert np.array_equal(H.d2h(H.h2d(pooled[5:], dev), pooled=False), pooled[5:])
     with pytest.raises(TypeError, match="no host array type"):
         H.d2h(torch.zeros(3, dtype=torch.bfloat16, device=dev))
     del owner, pooled
@@ -104,12 +105,12 @@ def test_gpu_model_weights_round_trip_without_pageable_copies():
     assert next(w.model.parameters()).is_cuda
     ws = w.get_weights()
     assert [a.dtype for a in ws] == [np.float32] * 4
-    ref = [p.detach().cpu().numpy().copy() for p in w.model.state_dict().values()]
-    assert all(np.array_equal(a, r) for a, r in zip(ws, ref))
+    # the weights were initialised on the device: compared there, each array sent back up
+    assert all(torch.equal(_dev(a).reshape(a.shape), p) for a, p in zip(ws, w.model.state_dict().values()))
     for form in ("numpy", "cpu", "cuda", "f64"):
         new = [np.asarray(a) * 2 + 1 for a in ws]
         give = {"numpy": new, "cpu": [torch.from_numpy(a) for a in new],
-                "cuda": [torch.from_numpy(a).cuda() for a in new],
+                "cuda": [_dev(a).reshape(a.shape) for a in new],
                 "f64": [a.astype(np.float64) for a in new]}[form]
         w.set_weights(give)
         got = w.get_weights()

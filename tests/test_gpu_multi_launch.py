@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-pytestmark = pytest.mark.gpu
+from gpu_copies import DEV, _dev, _item  # noqa: E402
 
-DEV = "cuda:0"
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -56,16 +56,16 @@ def test_multi_launch_schedule_vs_oracle(C, W, ranks, accumulate):
         assert len(plan.pairs) + len(plan.cross) > 32  # beyond one launch
         pg, ps, cross = plan_generators(plan, seed_of, offset=offset)
         init = rng.integers(0, 2**63, n, dtype=np.int64)
-        s = torch.from_numpy(init).to(DEV) if accumulate else torch.empty(n, dtype=torch.int64, device=DEV)
+        s = _dev(init) if accumulate else torch.empty(n, dtype=torch.int64, device=DEV)
         flags = torch.zeros(1, dtype=torch.int32, device=DEV)
-        K.fused_clients([torch.from_numpy(xs[c]).to(DEV) for c in plan.clients], [1.0] * len(plan.clients), pg, ps,
+        K.fused_clients([_dev(xs[c]) for c in plan.clients], [1.0] * len(plan.clients), pg, ps,
                         cross, plan.n_cross, s, accumulate=accumulate, flags=flags)
         torch.cuda.synchronize()
         exp = _rank_oracle(xs, names, seeds, plan, n, offset)
         if accumulate:
             exp += init.view(np.uint64)
         assert np.array_equal(K.as_u64(s), exp), (C, W, r)
-        assert int(flags.item()) == 0
+        assert int(_item(flags)) == 0
 
 
 def test_multi_launch_equals_per_client_fallback_and_flags_a_zero_draw():
@@ -101,7 +101,7 @@ def test_multi_launch_equals_per_client_fallback_and_flags_a_zero_draw():
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     K.fused_clients(xs, [1.0] * Lc, pg, ps, bad, plan.n_cross, s, flags=flags)
     torch.cuda.synchronize()
-    assert int(flags.item()) & L.SA_FLAG_PRG_REJECT
+    assert int(_item(flags)) & L.SA_FLAG_PRG_REJECT
 
 
 def test_config5_per_rank_schedule_full_size():
@@ -142,7 +142,7 @@ def test_config5_per_rank_schedule_full_size():
                  flags=flags)
         total += part
         torch.cuda.synchronize()
-        assert int(flags.item()) == 0
+        assert int(_item(flags)) == 0
         assert check_partial_sum_windows(part, xs, plan.clients, names, seeds, offset, joins=joins, k_random=3,
                                          seed=r) >= 8 * 4096
     torch.cuda.synchronize()

@@ -11,10 +11,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import DEV, _dev, _host, _item, _u64  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -51,10 +51,6 @@ def _oracle_masked(q, seeds, signs, offset):
     return out
 
 
-def _u64(t):
-    return _K().as_u64(t)
-
-
 # ---------------------------------------------------------------------------
 # single-client masking (sa_mask): the _Masker.mask replacement
 # ---------------------------------------------------------------------------
@@ -68,7 +64,7 @@ def test_mask_f32_bit_exact(n, nstreams):
     signs = [1 if j % 3 else -1 for j in range(nstreams)]
     offset = int(rng.integers(0, 1 << 40))
     exp = _oracle_masked(o.quantize(x), seeds, signs, offset)
-    xt = torch.from_numpy(x).to(DEV)
+    xt = _dev(x)
     out = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(1, dtype=torch.int64, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
@@ -76,7 +72,7 @@ def test_mask_f32_bit_exact(n, nstreams):
     torch.cuda.synchronize()
     assert np.array_equal(_u64(out), exp)
     assert int(_u64(dig)[0]) == o.digest(exp)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 @pytest.mark.parametrize("case", ["f64", "i64", "f32_wvec_f64", "f32_scalar_w", "f64_scalar_w", "i64_int_w",
@@ -108,10 +104,10 @@ def test_mask_other_types(case):
         if w is not None else x.dtype
     ct = ctype[cdt.type]
     if w is not None and np.ndim(w):
-        wvec = torch.from_numpy(np.asarray(w).astype(cdt)).to(DEV)
+        wvec = _dev(np.asarray(w).astype(cdt))
     exp = _oracle_masked(q, seeds, signs, 17)
     out = torch.empty(n, dtype=torch.int64, device=DEV)
-    K.mask(torch.from_numpy(x).to(DEV), out, _streams(seeds, signs, 17),
+    K.mask(_dev(x), out, _streams(seeds, signs, 17),
            weight=1.0 if w is None or np.ndim(w) else w, weight_vec=wvec, compute_dtype=ct)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(out), exp)
@@ -123,7 +119,7 @@ def test_quantize_edge_cases_bit_exact(golden_dir):
     for key in ("f32", "f64"):
         x = g[f"q_in_{key}"]
         out = torch.empty(x.size, dtype=torch.int64, device=DEV)
-        K.mask(torch.from_numpy(x).to(DEV), out, [])
+        K.mask(_dev(x), out, [])
         torch.cuda.synchronize()
         assert np.array_equal(_u64(out), g[f"q_out_{key}"]), key
 
@@ -142,14 +138,14 @@ def test_golden_round_from_fixture(golden_dir):
         st = [(L.pcg64_advance(L.pcg64_from_seed(seeds[name][p]), off), 1 if p > name else -1, j)
               for j, p in enumerate(peers)]
         out = torch.empty(n, dtype=torch.int64, device=DEV)
-        K.mask(torch.from_numpy(g["round_x"][i]).to(DEV), out, st)
+        K.mask(_dev(g["round_x"][i]), out, st)
         masked.append(out)
     s = K.sum_u64(masked, torch.empty(n, dtype=torch.int64, device=DEV))
     dec = K.decode(s, torch.empty(n, dtype=torch.float64, device=DEV))
     torch.cuda.synchronize()
     assert np.array_equal(np.stack([_u64(m) for m in masked]), g["round_masked"])
     assert np.array_equal(_u64(s), g["round_sum"])
-    assert np.array_equal(dec.cpu().numpy(), g["round_decoded"])
+    assert np.array_equal(_host(dec), g["round_decoded"])
 
 
 # ---------------------------------------------------------------------------
@@ -177,7 +173,7 @@ def test_fused_clients_bit_exact(C, n):
     names, xs, seeds, pg, ps = _fused_setup(C, n, offset)
     masked = o.secure_masked(xs, names, seeds=seeds, offset=offset)
     s_exp = o.server_sum(masked)
-    xt = [torch.from_numpy(x).to(DEV) for x in xs]
+    xt = [_dev(x) for x in xs]
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(C, dtype=torch.int64, device=DEV)
     mo = [torch.empty(n, dtype=torch.int64, device=DEV) for _ in range(C)]
@@ -188,10 +184,10 @@ def test_fused_clients_bit_exact(C, n):
     for c in range(C):
         assert np.array_equal(_u64(mo[c]), masked[c]), c
     assert [int(v) for v in _u64(dig)] == [o.digest(m) for m in masked]
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
     dec = K.decode(s, torch.empty(n, dtype=torch.float64, device=DEV))
     ref = o.decode(s_exp)
-    assert np.array_equal(dec.cpu().numpy(), ref)
+    assert np.array_equal(_host(dec), ref)
     assert np.abs(ref - np.sum(np.stack(xs).astype(np.float64), axis=0)).max() < C * 2.0**-18
     # the sum-only finish (no digests, no wire images: the bench's launch),
     # stored and accumulated
@@ -221,7 +217,7 @@ def test_fxp_bits_range(fxp):
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(C, dtype=torch.int64, device=DEV)
     mo = [torch.empty(n, dtype=torch.int64, device=DEV) for _ in range(C)]
-    xt = [torch.from_numpy(x).to(DEV) for x in xs]
+    xt = [_dev(x) for x in xs]
     K.fused_clients(xt, ws, pg, ps, [], 0, s, fxp_bits=fxp, digests=dig, masked_outs=mo)
     s2 = torch.empty(n, dtype=torch.int64, device=DEV)
     K.fused_clients(xt, ws, pg, ps, [], 0, s2, fxp_bits=fxp)
@@ -232,7 +228,7 @@ def test_fxp_bits_range(fxp):
     for c in range(C):
         assert np.array_equal(_u64(mo[c]), masked[c]), c
     assert [int(v) for v in _u64(dig)] == [o.digest(m) for m in masked]
-    assert np.array_equal(dec.cpu().numpy(), o.decode(s_exp, fxp, sum(ws)))
+    assert np.array_equal(_host(dec), o.decode(s_exp, fxp, sum(ws)))
     # per-client masking of the other payload types at this width
     rng = np.random.default_rng(fxp)
     seeds1 = [o.pair_seed(2, j) for j in (0, 1, 3)]
@@ -242,7 +238,7 @@ def test_fxp_bits_range(fxp):
                      ((rng.standard_normal(n) * 4).astype(np.float32), 0.3, torch.float32)):
         exp = _oracle_masked(o.quantize(x, w, fxp), seeds1, signs1, 99)
         out = torch.empty(n, dtype=torch.int64, device=DEV)
-        K.mask(torch.from_numpy(x).to(DEV), out, _streams(seeds1, signs1, 99), weight=w, compute_dtype=ct,
+        K.mask(_dev(x), out, _streams(seeds1, signs1, 99), weight=w, compute_dtype=ct,
                fxp_bits=fxp)
         torch.cuda.synchronize()
         assert np.array_equal(_u64(out), exp), ct
@@ -264,7 +260,7 @@ def test_fused_mixed_fast_and_exact_tiles(C):
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(C, dtype=torch.int64, device=DEV)
     mo = [torch.empty(n, dtype=torch.int64, device=DEV) for _ in range(C)]
-    K.fused_clients([torch.from_numpy(x).to(DEV) for x in xs], [1.0] * C, pg, ps, [], 0, s, digests=dig,
+    K.fused_clients([_dev(x) for x in xs], [1.0] * C, pg, ps, [], 0, s, digests=dig,
                     masked_outs=mo)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(s), o.server_sum(masked))
@@ -281,8 +277,8 @@ def test_fused_accumulate_and_weights():
     masked = o.secure_masked(xs, names, weights=[int(v) for v in w], seeds=seeds)
     exp = o.server_sum(masked)
     base = np.random.default_rng(1).integers(0, 2**63, n).astype(np.uint64)
-    s = torch.from_numpy(base.view(np.int64).copy()).to(DEV)
-    K.fused_clients([torch.from_numpy(x).to(DEV) for x in xs], w, pg, ps, [], 0, s, accumulate=True)
+    s = _dev(base.view(np.int64).copy())
+    K.fused_clients([_dev(x) for x in xs], w, pg, ps, [], 0, s, accumulate=True)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(s), base + exp)
 
@@ -307,7 +303,7 @@ def test_fused_with_cross_streams_matches_per_client():
                           1 if p > names[u] else -1, 0))
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(2, dtype=torch.int64, device=DEV)
-    K.fused_clients([torch.from_numpy(xs[u]).to(DEV) for u in local], [1.0, 1.0], pg, ps, cross, 2, s,
+    K.fused_clients([_dev(xs[u]) for u in local], [1.0, 1.0], pg, ps, cross, 2, s,
                     digests=dig)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(s), masked[0] + masked[1])
@@ -323,7 +319,7 @@ def test_sum_u64(k, n):
     K = _K()
     rng = np.random.default_rng(k * n)
     ins = [rng.integers(0, 2**64 - 1, n, dtype=np.uint64) for _ in range(k)]
-    ts = [torch.from_numpy(a.view(np.int64).copy()).to(DEV) for a in ins]
+    ts = [_dev(a.view(np.int64).copy()) for a in ins]
     out = K.sum_u64(ts, torch.empty(n, dtype=torch.int64, device=DEV))
     torch.cuda.synchronize()
     assert np.array_equal(_u64(out), o.server_sum(ins))
@@ -335,15 +331,15 @@ def test_decode_and_divisors():
     rng = np.random.default_rng(9)
     s = rng.integers(0, 2**64 - 1, n, dtype=np.uint64)
     s[:4] = [0, 2**63, 2**63 - 1, 2**64 - 1]
-    st = torch.from_numpy(s.view(np.int64).copy()).to(DEV)
+    st = _dev(s.view(np.int64).copy())
     for div in (1.0, 3.0, 640.0, 0.1):
         out = K.decode(st, torch.empty(n, dtype=torch.float64, device=DEV), divisor=div)
         torch.cuda.synchronize()
-        assert np.array_equal(out.cpu().numpy(), o.decode(s, 18, div if div != 1.0 else None)), div
+        assert np.array_equal(_host(out), o.decode(s, 18, div if div != 1.0 else None)), div
     dv = rng.integers(1, 100, n).astype(np.float64)
-    out = K.decode(st, torch.empty(n, dtype=torch.float64, device=DEV), divisor_vec=torch.from_numpy(dv).to(DEV))
+    out = K.decode(st, torch.empty(n, dtype=torch.float64, device=DEV), divisor_vec=_dev(dv))
     torch.cuda.synchronize()
-    assert np.array_equal(out.cpu().numpy(), o.decode(s, 18, dv))
+    assert np.array_equal(_host(out), o.decode(s, 18, dv))
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 7, 1024, 4099, 262_147, 3_000_001])
@@ -356,7 +352,7 @@ def test_server_kernels_sizes_and_alignment(n, shift):
     K = _K()
     rng = np.random.default_rng(n + 7 * shift)
     s = rng.integers(0, 2**64 - 1, n, dtype=np.uint64)
-    st = torch.from_numpy(s.view(np.int64).copy()).to(DEV)
+    st = _dev(s.view(np.int64).copy())
     # shift: the buffers start one element into a fresh allocation
     sb = torch.empty(n + 1, dtype=torch.int64, device=DEV)
     sb[shift:shift + n] = st
@@ -366,23 +362,23 @@ def test_server_kernels_sizes_and_alignment(n, shift):
     K.decode(sv, out, divisor=3.0)
     dv = rng.integers(1, 100, n).astype(np.float64)
     dvb = torch.empty(n + 1, dtype=torch.float64, device=DEV)
-    dvb[shift:shift + n] = torch.from_numpy(dv).to(DEV)
+    dvb[shift:shift + n] = _dev(dv)
     out2 = torch.empty(n + 1, dtype=torch.float64, device=DEV)[shift:shift + n]
     K.decode(sv, out2, divisor_vec=dvb[shift:shift + n])
     ws = [rng.standard_normal(n) for _ in range(3)]
     wb = []
     for w in ws:
         b = torch.empty(n + 1, dtype=torch.float64, device=DEV)
-        b[shift:shift + n] = torch.from_numpy(w).to(DEV)
+        b[shift:shift + n] = _dev(w)
         wb.append(b[shift:shift + n])
     fs = K.sum_f64(wb, torch.empty(n + 1, dtype=torch.float64, device=DEV)[shift:shift + n])
     torch.cuda.synchronize()
-    assert np.array_equal(out.cpu().numpy(), o.decode(s, 18, 3.0))
-    assert np.isnan(ob[(n if shift == 0 else 0)].item())  # nothing written past the vector
-    assert np.array_equal(out2.cpu().numpy(), o.decode(s, 18, dv))
-    assert np.array_equal(fs.cpu().numpy(), (ws[0] + ws[1]) + ws[2])
+    assert np.array_equal(_host(out), o.decode(s, 18, 3.0))
+    assert np.isnan(_item(ob[(n if shift == 0 else 0)]))  # nothing written past the vector
+    assert np.array_equal(_host(out2), o.decode(s, 18, dv))
+    assert np.array_equal(_host(fs), (ws[0] + ws[1]) + ws[2])
     if shift == 0:  # sa_sum_u64 needs 16-B aligned buffers
-        ins = [torch.from_numpy(rng.integers(0, 2**64 - 1, n, dtype=np.uint64).view(np.int64)).to(DEV)
+        ins = [_dev(rng.integers(0, 2**64 - 1, n, dtype=np.uint64).view(np.int64))
                for _ in range(5)]
         got = K.sum_u64(ins, torch.empty(n, dtype=torch.int64, device=DEV))
         torch.cuda.synchronize()
@@ -408,7 +404,7 @@ def test_prg_zero_draw_is_flagged():
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     K.mask(torch.zeros(64, device=DEV), out, [(g, 1, 0)], flags=flags)
     torch.cuda.synchronize()
-    assert int(flags.item()) & L.SA_FLAG_PRG_REJECT
+    assert int(_item(flags)) & L.SA_FLAG_PRG_REJECT
 
 
 # ---------------------------------------------------------------------------
@@ -453,7 +449,7 @@ def test_full_size_properties(C, n):
     assert torch.equal(s, s2)
     assert torch.equal(s, s3)
     assert torch.equal(dig, wdig)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
     # (3a) the bench's own launch (sum-only <C,0,4>) pinned to the oracle
     # directly: >= 8 windows of 4096 element positions (both ends, the
     # middle, random offsets), every pair stream jumped to the window start
@@ -463,9 +459,10 @@ def test_full_size_properties(C, n):
     # (3) oracle spot checks of individual masked elements at far offsets
     rng = np.random.default_rng(0)
     idx = np.concatenate([[0, 1, n - 1], rng.integers(0, n, 20)])
-    xh = [x[idx].cpu().numpy() for x in xs]
+    idx_d = _dev(idx)
+    xh = [_host(x[idx_d]) for x in xs]
     for c in range(C):
-        got = _u64(wire[c][idx])
+        got = _u64(wire[c][idx_d])
         for t, i in enumerate(idx):
             v = int(o.quantize(xh[c][t:t + 1])[0])
             for p in names:
@@ -476,7 +473,7 @@ def test_full_size_properties(C, n):
     # (4) decoded sum within C * 2^-18 of the float sum
     dec = K.decode(s, torch.empty(n, dtype=torch.float64, device=DEV))
     fsum = torch.stack(xs).double().sum(0)
-    assert float((dec - fsum).abs().max()) < C * 2.0**-18
+    assert float(_item((dec - fsum).abs().max())) < C * 2.0**-18
 
 
 def test_fused_fallback_for_uninstantiated_shape():
@@ -497,7 +494,7 @@ def test_fused_fallback_for_uninstantiated_shape():
     masked = o.secure_masked(xs, names, seeds=seeds, offset=7)
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(len(plan.clients), dtype=torch.int64, device=DEV)
-    K.fused_clients([torch.from_numpy(xs[c]).to(DEV) for c in plan.clients], [1.0] * len(plan.clients), pg, ps,
+    K.fused_clients([_dev(xs[c]) for c in plan.clients], [1.0] * len(plan.clients), pg, ps,
                     cross, plan.n_cross, s, digests=dig)
     torch.cuda.synchronize()
     exp = np.zeros(n, dtype=np.uint64)
@@ -517,7 +514,7 @@ def test_fused_more_than_8_clients_falls_back():
     masked = o.secure_masked(xs, names, seeds=seeds, offset=9)
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(C, dtype=torch.int64, device=DEV)
-    K.fused_clients([torch.from_numpy(x).to(DEV) for x in xs], [1.0] * C, pg, ps, [], 0, s, digests=dig)
+    K.fused_clients([_dev(x) for x in xs], [1.0] * C, pg, ps, [], 0, s, digests=dig)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(s), o.server_sum(masked))
     assert [int(v) for v in _u64(dig)] == [o.digest(m) for m in masked]
@@ -538,17 +535,17 @@ def test_fused_many_pair_shared_bit_exact(C, n):
     names, xs, seeds, pg, ps = _fused_setup(C, n, offset)
     w = [1 + c % 3 for c in range(C)]
     exp = o.server_sum(o.secure_masked(xs, names, weights=w, seeds=seeds, offset=offset))
-    xt = [torch.from_numpy(x).to(DEV) for x in xs]
+    xt = [_dev(x) for x in xs]
     s = torch.empty(n, dtype=torch.int64, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     K.fused_clients(xt, [float(v) for v in w], pg, ps, [], 0, s, flags=flags)
     base = np.random.default_rng(C).integers(0, 2**63, n, dtype=np.uint64)
-    acc = torch.from_numpy(base.view(np.int64).copy()).to(DEV)
+    acc = _dev(base.view(np.int64).copy())
     K.fused_many(xt, [float(v) for v in w], pg, ps, acc, accumulate=True)
     torch.cuda.synchronize()
     assert np.array_equal(_u64(s), exp)
     assert np.array_equal(_u64(acc), base + exp)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 def test_fused_many_full_size_32_clients():
@@ -580,7 +577,7 @@ def test_fused_many_full_size_32_clients():
     torch.cuda.synchronize()
     assert torch.equal(s, q_sum)
     assert torch.equal(s, s2)
-    assert int(flags.item()) == 0
+    assert int(_item(flags)) == 0
 
 
 def test_fused_many_padding_streams_cancel():
@@ -589,7 +586,7 @@ def test_fused_many_padding_streams_cancel():
     K, L = _K(), _L()
     n = 10_007
     base = np.random.default_rng(5).integers(0, 2**64 - 1, n, dtype=np.uint64)
-    s = torch.from_numpy(base.view(np.int64).copy()).to(DEV)
+    s = _dev(base.view(np.int64).copy())
     clients = (L.LocalClient * 8)()
     for c in range(8):
         clients[c].x, clients[c].weight, clients[c].masked_out = None, 1.0, None
@@ -629,7 +626,7 @@ def test_chunked_launch_past_4gib():
         assert torch.equal(mo[c], outs[c])
     for lo in (0, chunk - 40, n - 40):
         m = o.mask_stream(sd, 40, lo)
-        q0 = o.quantize(xs[0][lo:lo + 40].cpu().numpy())
+        q0 = o.quantize(_host(xs[0][lo:lo + 40]))
         assert np.array_equal(_u64(outs[0][lo:lo + 40]), q0.view(np.uint64) + m), lo
     del xs, outs, mo
     torch.cuda.empty_cache()
@@ -642,7 +639,7 @@ def test_launches_capture_into_a_graph():
     K, L = _K(), _L()
     C, n = 4, 100_003
     names, xs, seeds, pg, ps = _fused_setup(C, n, 0)
-    xd = [torch.from_numpy(x).to(DEV) for x in xs]
+    xd = [_dev(x) for x in xs]
     s_e = torch.empty(n, dtype=torch.int64, device=DEV)
     d_e = torch.empty(n, dtype=torch.float64, device=DEV)
     K.fused_clients(xd, [1.0] * C, pg, ps, [], 0, s_e)

@@ -16,6 +16,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import _dev, _u64  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -160,7 +161,7 @@ def test_per_element_weights_and_device_tensors_keep_the_one_shot_path(monkeypat
     x = (rng.standard_normal(n) * 0.1).astype(np.float32)
     wire, _ = P.mask_payload(maskers["alice"], x, w, gpu=0)
     assert np.array_equal(wire.u64, _expected([x], w, "alice", seeds, 0))
-    t = torch.from_numpy(x).to("cuda:0")
+    t = _dev(x)
     wire, _ = P.mask_payload(maskers["alice"], t, None, gpu=0)
     assert np.array_equal(wire.u64, _expected([x], None, "alice", seeds, 0))
     assert calls == []
@@ -254,7 +255,7 @@ def test_in_process_large_general_payloads(kind, C, monkeypatch):
         for data in rounds:
             got = rv(agg.average([p(lambda d=d: d)() for p, d in zip(pyus, data)], axis=0, weights=weights))
             # the one-shot general path keeps its digests on the device
-            outs.append((got, [d.cpu().numpy().view(np.uint64).copy() for d in agg.last_digests if d is not None]))
+            outs.append((got, [_u64(d).copy() for d in agg.last_digests if d is not None]))
         pos = {nm: {q: agg._maskers[nm].position(q) for q in names if q != nm} for nm in names}
         return outs, pos
 
@@ -369,7 +370,7 @@ def test_in_process_large_rejection_replays_on_numpys_stream(dtype):
         got = rv(agg.sum([p(lambda x=x: x)() for p, x in zip(pyus, xs)], axis=0))
         masked, ssum = ora.round(xs)
         assert np.array_equal(got, o.decode(ssum)), rnd
-        dig = agg.last_digests[-1].cpu().numpy().view(np.uint64)
+        dig = _u64(agg.last_digests[-1])
         assert [int(d) for d in dig] == [o.digest(m) for m in masked]
     assert agg._maskers["alice"].position("bob") == 2 * n + 1
     assert agg._maskers["alice"].position("carol") == 2 * n

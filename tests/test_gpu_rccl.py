@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,7 +41,7 @@ def comm():
 def test_rccl_world1_reduce_is_identity(comm):
     rng = np.random.default_rng(1)
     a = rng.integers(0, 2**64 - 1, 100_003, dtype=np.uint64)
-    send = torch.from_numpy(a.view(np.int64).copy()).cuda()
+    send = _dev(a.view(np.int64).copy())
     recv = torch.empty_like(send)
     comm.reduce_u64(send, recv, root=0)
     recv2 = torch.empty_like(send)
@@ -74,12 +76,12 @@ def test_pipelined_masked_sum_matches_oracle(comm, chunks):
     recv = torch.empty(n, dtype=torch.int64, device=dev)
     dig = torch.zeros(len(plan.clients), dtype=torch.int64, device=dev)
     kev = []
-    pipe.run([torch.from_numpy(xs[c]).to(dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
+    pipe.run([_dev(xs[c], device=dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
              plan.n_cross, s, recv, digests=dig, kernel_events=kev)
     torch.cuda.synchronize()
     assert len(kev) == len(pipe.bounds)
-    assert np.array_equal(recv.cpu().numpy().view(np.uint64), exp)
-    assert [int(v) for v in dig.cpu().numpy().view(np.uint64)] == [o.digest(masked[c]) for c in plan.clients]
+    assert np.array_equal(_u64(recv), exp)
+    assert [int(v) for v in _u64(dig)] == [o.digest(masked[c]) for c in plan.clients]
 
 
 def test_back_to_back_rounds_without_join(comm):
@@ -109,11 +111,11 @@ def test_back_to_back_rounds_without_join(comm):
         exps.append(exp)
         gens = [plan_generators(plan, seed_of, offset=r * n + lo) for lo, _ in pipe.bounds]
         recvs.append(torch.empty(n, dtype=torch.int64, device=dev))
-        pipe.run([torch.from_numpy(xs[c]).to(dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
+        pipe.run([_dev(xs[c], device=dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
                  plan.n_cross, s, recvs[-1], join=False)
     torch.cuda.synchronize()
     for r in range(3):
-        assert np.array_equal(recvs[r].cpu().numpy().view(np.uint64), exps[r]), r
+        assert np.array_equal(_u64(recvs[r]), exps[r]), r
 
 
 def test_rccl_world1_reduce_scatter_and_gather(comm):
@@ -121,15 +123,15 @@ def test_rccl_world1_reduce_scatter_and_gather(comm):
     shard is the identity (in place and out of place), the gather a copy."""
     rng = np.random.default_rng(2)
     a = rng.integers(0, 2**64 - 1, 70_001, dtype=np.uint64)
-    send = torch.from_numpy(a.view(np.int64).copy()).cuda()
+    send = _dev(a.view(np.int64).copy())
     out = torch.empty_like(send)
     comm.reduce_scatter_u64(send, out)
     comm.reduce_scatter_u64(send, send)  # in place
-    f = torch.from_numpy(rng.standard_normal(70_001)).cuda()
+    f = _dev(rng.standard_normal(70_001))
     g = torch.empty_like(f)
     comm.gather_f64(f, g, root=0)
     torch.cuda.synchronize()
-    assert torch.equal(out, send) and torch.equal(send.cpu(), torch.from_numpy(a.view(np.int64)))
+    assert torch.equal(out, send) and np.array_equal(_host(send), a.view(np.int64))
     assert torch.equal(g, f)
 
 
@@ -169,11 +171,11 @@ def test_sharded_server_pipeline_world1(comm, chunks, exchange):
         exps.append(o.decode(o.server_sum(o.secure_masked(xs, names, seeds=seeds, offset=r * n)), divisor=4.0))
         gens = [plan_generators(plan, seed_of, offset=r * n + lo) for lo, _ in pipe.bounds]
         decs.append(torch.empty(pipe.buffer_len, dtype=torch.float64, device=dev))
-        pipe.run([torch.from_numpy(x).to(dev) for x in xs], [1.0] * C, gens, plan.n_cross, s, None,
+        pipe.run([_dev(x, device=dev) for x in xs], [1.0] * C, gens, plan.n_cross, s, None,
                  dec=decs[-1], divisor=4.0, gather=True, join=False)
     torch.cuda.synchronize()
     for r in range(2):
-        assert np.array_equal(decs[r][:n].cpu().numpy(), exps[r]), r
+        assert np.array_equal(_host(decs[r][:n]), exps[r]), r
 
 
 @pytest.mark.parametrize("exchange", ["reduce", "sharded", "direct"])
@@ -201,13 +203,13 @@ def test_pipelined_world1_at_1m_matches_oracle_server_sum(comm, exchange):
     s = torch.zeros(pipe.buffer_len, dtype=torch.int64, device=dev)
     dec = torch.zeros(pipe.buffer_len, dtype=torch.float64, device=dev) if exchange != "reduce" else None
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    pipe.run([torch.from_numpy(x).to(dev) for x in xs], [1.0] * C, gens, plan.n_cross, s, None, flags=flags,
+    pipe.run([_dev(x, device=dev) for x in xs], [1.0] * C, gens, plan.n_cross, s, None, flags=flags,
              dec=dec)
     torch.cuda.synchronize()
-    assert int(flags.item()) == 0
-    assert np.array_equal(s[:n].cpu().numpy().view(np.uint64), exp)
+    assert int(_item(flags)) == 0
+    assert np.array_equal(_u64(s[:n]), exp)
     if dec is not None:
-        assert np.array_equal(dec[:n].cpu().numpy(), o.decode(exp))
+        assert np.array_equal(_host(dec[:n]), o.decode(exp))
 
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

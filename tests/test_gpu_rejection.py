@@ -19,6 +19,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 A = o.PCG64_MULT
@@ -134,12 +135,12 @@ def test_find_zero_and_shift_match_numpy(k):
     flags = torch.zeros(1, dtype=torch.int32, device="cuda:0")
     K.mask(x, out, [(g, -1, 0)], flags=flags)
     torch.cuda.synchronize()
-    assert int(flags.item()) & L.SA_FLAG_PRG_REJECT
+    assert int(_item(flags)) & L.SA_FLAG_PRG_REJECT
     K.stream_shift(out, g, -1, k, 1)
     dig = torch.zeros(1, dtype=torch.int64, device="cuda:0")
     K.xor_digest(out, dig)
     m = o.generator_from_state(s, inc).integers(o.INT64_MIN, o.INT64_MAX, size=n).astype(np.uint64)
-    exp = o.quantize(x.cpu().numpy()) - m
+    exp = o.quantize(_host(x)) - m
     assert np.array_equal(K.as_u64(out), exp)
     assert int(K.as_u64(dig)[0]) == o.digest(exp)
 
@@ -176,16 +177,16 @@ def test_plugin_round_with_rejection_matches_numpy(mode):
         if mode == "host_fused":
             objs = [p(lambda x=x: x)() for p, x in zip(pyus, xs)]
         else:
-            objs = [p(lambda x=x: torch.from_numpy(x).cuda())() for p, x in zip(pyus, xs)]
+            objs = [p(lambda x=x: _dev(x))() for p, x in zip(pyus, xs)]
         got = reveal(agg.sum(objs, axis=0))
-        got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+        got = _host(got) if isinstance(got, torch.Tensor) else got
         masked, ssum = ora.round(xs)
         assert np.array_equal(got, o.decode(ssum)), (mode, rnd)
-        assert [int(v) for v in agg.last_digests[0].cpu().numpy().view(np.uint64)] == \
+        assert [int(v) for v in _u64(agg.last_digests[0])] == \
             [o.digest(m) for m in masked], (mode, rnd)
         if keep:
             for c in range(len(NAMES)):
-                assert np.array_equal(agg.last_masked[0][c].cpu().numpy().view(np.uint64), masked[c]), (mode, rnd, c)
+                assert np.array_equal(_u64(agg.last_masked[0][c]), masked[c]), (mode, rnd, c)
     # the pair stream consumed one raw draw more than the others
     assert agg._maskers["bob"].position("dave") == 2 * n + 1
     assert agg._maskers["dave"].position("bob") == 2 * n + 1
@@ -213,7 +214,7 @@ def test_layers_after_a_rejection_use_shifted_positions():
     exp = o.decode(ssum, divisor=10)
     assert np.array_equal(np.concatenate(got), exp)
     for c in range(len(NAMES)):
-        img = np.concatenate([agg.last_masked[li][c].cpu().numpy().view(np.uint64) for li in range(2)])
+        img = np.concatenate([_u64(agg.last_masked[li][c]) for li in range(2)])
         assert np.array_equal(img, masked[c])
 
 
@@ -240,9 +241,9 @@ def test_many_parties_rejection_replays_per_party(host):
     rng = np.random.default_rng(12)
     for rnd in range(2):
         xs = [(rng.standard_normal(n) * 1e-2).astype(np.float32) for _ in names]
-        objs = [p(lambda x=x: x if host else torch.from_numpy(x).cuda())() for p, x in zip(pyus, xs)]
+        objs = [p(lambda x=x: x if host else _dev(x))() for p, x in zip(pyus, xs)]
         got = reveal(agg.sum(objs, axis=0))
-        got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+        got = _host(got) if isinstance(got, torch.Tensor) else got
         _, ssum = ora.round(xs)
         assert np.array_equal(got, o.decode(ssum)), (host, rnd)
     assert agg._maskers["p03"].position("p08") == 2 * n + 1

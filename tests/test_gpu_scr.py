@@ -198,10 +198,10 @@ def test_compressor_takes_the_device_path():
     bias = torch.arange(5, dtype=torch.float32, device=DEV)
     sparse, res = Cz.scr_step(bias, None, None, 2.0)
     assert torch.equal(sparse, bias) and sparse.data_ptr() != bias.data_ptr() and not res.any()
-    ints = torch.tensor([[4, -2, 2], [1, 0, 0], [4, 2, 0]], device=DEV)
+    ints = _dev(np.array([[4, -2, 2], [1, 0, 0], [4, 2, 0]])).reshape(3, 3)
     sparse, res = Cz.scr_step(ints, None, None, 0.3)
     assert sparse.is_cuda and sparse.dtype == torch.int64
-    assert sparse.tolist() == [[4, -2, 0], [0, 0, 0], [4, 2, 0]] and torch.equal(sparse + res, ints)
+    assert _host(sparse).tolist() == [[4, -2, 0], [0, 0, 0], [4, 2, 0]] and torch.equal(sparse + res, ints)
 
 
 def test_refusals_launch_nothing():

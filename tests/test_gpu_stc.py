@@ -225,4 +225,4 @@ def test_refusals_launch_nothing():
     torch.cuda.synchronize()
     assert torch.equal(t, before)
     with pytest.raises(ValueError):
-        K.stc(t.cpu(), None, None, 1, t, t, scratch=s)
+        K.stc(t.cpu(), None, None, 1, t, t, scratch=s)  # pageable: the CPU tensor is the argument under test

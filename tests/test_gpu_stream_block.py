@@ -32,9 +32,9 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-pytestmark = pytest.mark.gpu
+from gpu_copies import DEV, _dev, _item  # noqa: E402
 
-DEV = "cuda:0"
+pytestmark = pytest.mark.gpu
 SMALL = (1, 511, 513)
 # (clients, ranks, rank under test, the long length)
 FUSED = {(8, 0): (8, 1, 0, 600_001), (4, 4): (8, 2, 1, 800_001), (2, 6): (8, 4, 2, 1_400_001),
@@ -97,11 +97,11 @@ def _run_fused(C, W, rank, n, full):
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     dig = torch.zeros(Lc, dtype=torch.int64, device=DEV) if full else None
     mo = [torch.empty(n, dtype=torch.int64, device=DEV) for _ in range(Lc)] if full else None
-    K.fused_clients([torch.from_numpy(x.copy()).to(DEV) for x in xs], [1.0] * Lc, pg, ps, cross, plan.n_cross, s,
+    K.fused_clients([_dev(x.copy()) for x in xs], [1.0] * Lc, pg, ps, cross, plan.n_cross, s,
                     digests=dig, flags=flags, masked_outs=mo)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(s), o.server_sum(masked)), "masked sum"
-    assert int(flags.item()) == 0, "reject flag"
+    assert int(_item(flags)) == 0, "reject flag"
     if full:
         for c in range(Lc):
             assert np.array_equal(K.as_u64(mo[c]), masked[c]), f"masked vector of local client {c}"
@@ -166,15 +166,15 @@ def test_single_client_continue_mode_equals_oracle(n):
     acc = torch.zeros(n, dtype=torch.int64, device=DEV)
     dig = torch.zeros(1, dtype=torch.int64, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
-    K.mask(torch.from_numpy(x).to(DEV), out, streams, sum_accum=acc, digest=dig, flags=flags)
-    prior = torch.from_numpy(q.view(np.int64)).to(DEV)
+    K.mask(_dev(x), out, streams, sum_accum=acc, digest=dig, flags=flags)
+    prior = _dev(q.view(np.int64))
     K.mask(None, prior, streams, flags=flags)
     torch.cuda.synchronize()
     assert np.array_equal(K.as_u64(out), exp), "masked vector"
     assert np.array_equal(K.as_u64(acc), exp), "sum accumulator"
     assert int(K.as_u64(dig)[0]) == o.digest(exp), "digest"
     assert np.array_equal(K.as_u64(prior), exp), "continued from the caller's vector"
-    assert int(flags.item()) == 0, "reject flag"
+    assert int(_item(flags)) == 0, "reject flag"
 
 
 def test_zero_draw_in_a_group_raises_the_reject_flag():
@@ -195,7 +195,7 @@ def test_zero_draw_in_a_group_raises_the_reject_flag():
         bad[-1] = L.PCG64.of(*forced_zero_state(k))
         s = torch.empty(n, dtype=torch.int64, device=DEV)
         flags = torch.zeros(1, dtype=torch.int32, device=DEV)
-        K.fused_clients([torch.from_numpy(x.copy()).to(DEV) for x in xs], [1.0] * C, bad, ps, cross, 0, s, flags=flags)
+        K.fused_clients([_dev(x.copy()) for x in xs], [1.0] * C, bad, ps, cross, 0, s, flags=flags)
         torch.cuda.synchronize()
-        got.append(int(flags.item()) & L.SA_FLAG_PRG_REJECT)
+        got.append(int(_item(flags)) & L.SA_FLAG_PRG_REJECT)
     assert got == [L.SA_FLAG_PRG_REJECT, 0]

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _dev, _host, _item, _u64  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -44,14 +46,14 @@ def test_all_ranks_sum_to_the_oracle(W, chunks):
         part = torch.empty(n, dtype=torch.int64, device=dev)
         dig = torch.zeros(len(plan.clients), dtype=torch.int64, device=dev)
         flags = torch.zeros(1, dtype=torch.int32, device=dev)
-        pipe.run([torch.from_numpy(xs[c]).to(dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
+        pipe.run([_dev(xs[c], device=dev) for c in plan.clients], [1.0] * len(plan.clients), gens,
                  plan.n_cross, part, None, digests=dig, flags=flags)
         total += part
         torch.cuda.synchronize()
-        assert int(flags.item()) == 0
-        for c, d in zip(plan.clients, dig.cpu().numpy().view(np.uint64)):
+        assert int(_item(flags)) == 0
+        for c, d in zip(plan.clients, _u64(dig)):
             digests[c] = int(d)
-    assert np.array_equal(total.cpu().numpy().view(np.uint64), exp)
+    assert np.array_equal(_u64(total), exp)
     assert [digests[c] for c in range(C)] == [o.digest(m) for m in masked]
     # the masks cancel: the decoded total is the plain quantized sum
     assert np.array_equal(exp, o.server_sum([o.quantize(x) for x in xs]))
@@ -130,7 +132,7 @@ def test_per_rank_shapes_full_size(W):
             wire.append(out)
         wsum = K.sum_u64(wire, torch.empty(n, dtype=torch.int64, device=dev))
         torch.cuda.synchronize()
-        assert int(flags.item()) == 0
+        assert int(_item(flags)) == 0
         assert torch.equal(part, wsum), r
         assert torch.equal(dig, wdig), r
         del wsum
@@ -143,8 +145,8 @@ def test_per_rank_shapes_full_size(W):
         assert torch.equal(s1, part), r
         for i, c in enumerate(plan.clients):
             assert torch.equal(imgs[i], wire[i]), (r, c)
-            got = imgs[i][torch.from_numpy(idx).to(dev)].cpu().numpy().view(np.uint64)
-            xh = xs[c][torch.from_numpy(idx).to(dev)].cpu().numpy()
+            got = _u64(imgs[i][_dev(idx, device=dev)])
+            xh = _host(xs[c][_dev(idx, device=dev)])
             for t, e in enumerate(idx):
                 v = int(o.quantize(xh[t:t + 1])[0])
                 for p in names:
@@ -184,11 +186,11 @@ def test_element_sharding_slices_match_oracle(world):
         e0, m, k = element_shard(n, world, r)
         pg, ps, cross = plan_generators(plan, seed_of, offset=rnd * n + e0)
         s = torch.zeros(k, dtype=torch.int64, device=dev)
-        K.fused_clients([torch.from_numpy(x[e0:e0 + m].copy()).to(dev) for x in xs], [1.0] * C, pg, ps, cross, 0,
+        K.fused_clients([_dev(x[e0:e0 + m].copy(), device=dev) for x in xs], [1.0] * C, pg, ps, cross, 0,
                         s[:m])
         d = K.decode(s, torch.empty(k, dtype=torch.float64, device=dev))
         torch.cuda.synchronize()
-        got_s.append(s[:m].cpu().numpy().view(np.uint64))
-        got_d.append(d[:m].cpu().numpy())
+        got_s.append(_u64(s[:m]))
+        got_d.append(_host(d[:m]))
     assert np.array_equal(np.concatenate(got_s), ssum)
     assert np.array_equal(np.concatenate(got_d), o.decode(ssum))

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _dev, _u64  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +24,12 @@ def test_xor_digest_bit_exact(n, off):
 
     rng = np.random.default_rng(n + off)
     host = rng.integers(0, 2**63, n + off, dtype=np.int64) * 2 + 1
-    dev = torch.from_numpy(host).to("cuda:0")
+    dev = _dev(host)
     seed = np.int64(0x1234_5678_9ABC_DEF)
-    dig = torch.tensor([seed], dtype=torch.int64, device="cuda:0")
+    dig = _dev(np.array([seed], dtype=np.int64))
     K.xor_digest(dev[off:], dig)
     want = np.bitwise_xor.reduce(host[off:].view(np.uint64)) ^ np.uint64(seed)
-    assert int(dig.cpu().numpy().view(np.uint64)[0]) == int(want)
+    assert int(_u64(dig)[0]) == int(want)
 
 
 def test_xor_digest_rate():

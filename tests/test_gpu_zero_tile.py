@@ -11,6 +11,8 @@ from oracle import secagg as o
 from test_gpu_rejection import forced_zero_state
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _item  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -30,7 +32,7 @@ def _launch(K, L, n, L_clients, gens, signs, cross, n_cross):
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     K.fused_clients(xs, [1.0] * L_clients, gens, signs, cross, n_cross, s, flags=flags)
     torch.cuda.synchronize()
-    return int(flags.item())
+    return int(_item(flags))
 
 
 @pytest.mark.parametrize("zero_pair", [None, 0, 27])
@@ -139,7 +141,7 @@ def test_every_stream_of_the_timed_shapes_at_exact_positions(world, pos, big_inp
             xs = [big_input[:n]] * Lc  # the clients' values do not enter the flag
             K.fused_clients(xs, [1.0] * Lc, pg, ps, cross, X, s[:n], flags=flags)
             torch.cuda.synchronize()
-            got = bool(int(flags.item()) & L.SA_FLAG_PRG_REJECT)
+            got = bool(int(_item(flags)) & L.SA_FLAG_PRG_REJECT)
             if got != want:
                 missed.append((j, n, got))
     assert not missed, f"world {world} (<{Lc},{X}>) zero at element {k}: (stream, n, flag) wrong: {missed}"
@@ -158,7 +160,7 @@ def _flag_matrix(K, L, launch, n_streams, k):
             flags.zero_()
             launch(j, zero, n, flags)
             torch.cuda.synchronize()
-            got = bool(int(flags.item()) & L.SA_FLAG_PRG_REJECT)
+            got = bool(int(_item(flags)) & L.SA_FLAG_PRG_REJECT)
             if got != want:
                 missed.append((j, n, got))
     return missed

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_copies import _u64  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,7 +74,7 @@ def test_integration_stub_mask_reproduces_numpy_rejection():
     rng = np.random.default_rng(3)
     for n in (4099, 3001):  # the zero lands in the first call; the second checks the shifted position
         x = (rng.standard_normal(n) * 1e-2).astype(np.float32)
-        got = p.mask(x).cpu().numpy().view(np.uint64)
+        got = _u64(p.mask(x))
         m = gen.integers(o.INT64_MIN, o.INT64_MAX, size=n).astype(np.uint64)
         assert np.array_equal(got, o.quantize(x) + m)  # bob sorts after alice: +m
     assert p.pos["bob"] == 4099 + 3001 + 1  # numpy consumed one raw draw more
