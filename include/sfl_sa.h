@@ -891,6 +891,80 @@ int sa_flame_stats(const void* const* x, int n_clients, int x_type, uint64_t n, 
 int sa_flame_combine(const void* const* x, const double* scale, const double* weight, int n_clients, int x_type,
                      uint64_t n, const void* median, double divisor, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* FedSMP: sparsified model perturbation (examples/security/h_gia/      */
+/* FedSMP_defense/FedSMP_torch.py:105-119 the worker, :193-201 the      */
+/* server's mask).  A worker uploads                                    */
+/*   w0 + mask * GaussianModelDP(mask * (w1 - w0) / (p + 1e-6))         */
+/* for the round's weights w0, its trained weights w1 and a random 0/1  */
+/* mask of keep ratio p.  Here (sfl_amd/security/privacy/smp.py has the */
+/* host form):                                                          */
+/*   mask    keyed, never shipped: element e of a layer has stream      */
+/*           index i = counter0 + e (counter0 % 4 == 0: the sum of      */
+/*           ceil(n / 4) * 4 over the float32 layers before it, the     */
+/*           layout of sa_dp's counter0); w_i = word i & 3 of           */
+/*           Philox4x32-10 on the counter block (lo32(i >> 2),          */
+/*           hi32(i >> 2), 1, 0) under the key words (lo32(key),        */
+/*           hi32(key)); the element is KEPT iff w_i < threshold,       */
+/*           compared in 64 bits, threshold = min(2^32, int(p * 2^32)): */
+/*           2^32 keeps everything, 0 nothing.  The 1 in the third      */
+/*           counter word keeps the mask's words apart from the DP      */
+/*           noise's (0 there) under one key.                           */
+/*   d       = kept ? (w1 - w0) / divisor : +0, float32, the subtract   */
+/*           and the IEEE division each rounded once; divisor =         */
+/*           np.float32(p + 1e-6), the double sum rounded once.         */
+/*   norm    a layer's squared norm is sa_sumsq_f32's definition        */
+/*           applied to d: sa_smp_sumsq_f32 is bit for bit sa_sumsq_f32 */
+/*           of sa_smp_delta_f32's output (the same grid, lane map,     */
+/*           order of additions and final step; one body, two loaders). */
+/*   t       = d * scale + (z * sigma) / num_updates, sa_dp_perturb_f32 */
+/*           on d: z the normal of noise index dp->counter0 + e; the    */
+/*           normals of dropped elements are skipped, never reused.     */
+/*   out     = kept ? w0 + t : w0 (a dropped element has w0's bits);    */
+/*           without a dp, kept ? w0 + d : w0.                          */
+/* Differences from the reference, on purpose: float32 throughout (its  */
+/* int64 mask promotes the update, the norm and the upload to float64); */
+/* a select where it multiplies by 0 (0 * inf is NaN there, and a zero  */
+/* weight can change sign); the mask from (key, p) instead of an int64  */
+/* array from numpy's unseeded global stream (parity for the mask is    */
+/* distributional, as for the noise).                                   */
+/* float32 vectors are 16-byte aligned; n == 0 returns before they are  */
+/* looked at.  counter0 % 4 != 0, threshold > 2^32, a divisor that is   */
+/* not positive (where the entry divides), null or misaligned vectors   */
+/* and an n beyond the tile grid are refused before any launch.         */
+/* Everything is stream-ordered, allocates nothing, uses no atomics and */
+/* gives the same bits on every run.  ABI version 3 (additive).         */
+/* ------------------------------------------------------------------ */
+typedef struct sa_smp {
+  uint64_t key;       /* Philox key of the round's mask */
+  uint64_t counter0;  /* stream index of element 0 (multiple of 4) */
+  uint64_t threshold; /* kept iff word < threshold; at most 2^32 */
+  float divisor;      /* np.float32(p + 1e-6) */
+} sa_smp;
+
+/* out[e] = 1 if element e is kept, else 0: n bytes of host memory (no GPU needed) */
+int sa_smp_mask_host(const sa_smp* smp, uint64_t n, uint8_t* out);
+
+/* the same bytes on the device */
+int sa_smp_mask(const sa_smp* smp, uint64_t n, uint8_t* out, void* stream);
+
+/* out = d, materialised (out may alias w1) */
+int sa_smp_delta_f32(const float* w0, const float* w1, uint64_t n, const sa_smp* smp, float* out, void* stream);
+
+/* *sumsq (+)= the squared norm of d as sa_sumsq_f32 forms it, d never stored;
+ * `partials` is caller scratch of SA_DP_PARTIALS doubles */
+int sa_smp_sumsq_f32(const float* w0, const float* w1, uint64_t n, const sa_smp* smp, double* partials,
+                     double* sumsq, int accumulate, void* stream);
+
+/* the upload in one pass: out = kept ? w0 + t : w0; dp may be NULL (t = d);
+ * out may alias w1 */
+int sa_smp_perturb_f32(const float* w0, const float* w1, uint64_t n, const sa_smp* smp, const sa_dp* dp, float* out,
+                       void* stream);
+
+/* out = kept ? w0 + t : w0 for a t formed elsewhere (sa_smp_delta_f32, then
+ * any model-level DP): the last step of the unfused path; out may alias t */
+int sa_smp_finish_f32(const float* w0, const float* t, uint64_t n, const sa_smp* smp, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

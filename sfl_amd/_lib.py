@@ -48,6 +48,8 @@ EXPORTED = (
     "sa_kmeans_scratch_bytes", "sa_kmeans_hist", "sa_kmeans_step", "sa_kmeans_labels", "sa_dequant_lut",
     "sa_flame_scratch_bytes", "sa_flame_stats", "sa_flame_combine",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
+    "sa_smp_mask_host", "sa_smp_mask", "sa_smp_delta_f32", "sa_smp_sumsq_f32", "sa_smp_perturb_f32",
+    "sa_smp_finish_f32",
 )
 
 
@@ -97,6 +99,11 @@ class DPSecure(C.Structure):
     _fields_ = [("sumsq", C.c_void_p), ("sumsq_layer", C.c_void_p), ("l2_norm_clip", C.c_double),
                 ("noise_std", C.c_double), ("num_updates", C.c_float), ("key", C.c_uint32 * 8),
                 ("nonce", C.c_uint64), ("counter0", C.c_uint64)]
+
+
+class SMP(C.Structure):
+    """sa_smp: FedSMP's keyed mask for one layer."""
+    _fields_ = [("key", C.c_uint64), ("counter0", C.c_uint64), ("threshold", C.c_uint64), ("divisor", C.c_float)]
 
 
 _lock = threading.Lock()
@@ -176,6 +183,12 @@ def _declare(lib):
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]
     lib.sa_hb_normals_f64.argtypes = [vp, u64, dbl, vp, vp]
+    lib.sa_smp_mask_host.argtypes = [P(SMP), u64, vp]
+    lib.sa_smp_mask.argtypes = [P(SMP), u64, vp, vp]
+    lib.sa_smp_delta_f32.argtypes = [vp, vp, u64, P(SMP), vp, vp]
+    lib.sa_smp_sumsq_f32.argtypes = [vp, vp, u64, P(SMP), vp, vp, i32, vp]
+    lib.sa_smp_perturb_f32.argtypes = [vp, vp, u64, P(SMP), P(DP), vp, vp]
+    lib.sa_smp_finish_f32.argtypes = [vp, vp, u64, P(SMP), vp, vp]
     for name in EXPORTED:
         if name not in ("sa_last_error",):
             getattr(lib, name).restype = i32
@@ -302,4 +315,14 @@ def topk_random_keys_host(seed: int, n: int):
     out = np.empty(n, dtype=np.uint64)
     check(lib().sa_topk_random_keys_host(int(seed) & ((1 << 64) - 1), n, out.ctypes.data_as(C.c_void_p)),
           "sa_topk_random_keys_host")
+    return out
+
+
+def smp_mask_host(smp: SMP, n: int):
+    """FedSMP's mask of ``n`` elements under ``smp`` as uint8 (1: kept), computed on the host
+    (sa_smp_mask_host: what sa_smp_mask writes on the device)."""
+    import numpy as np
+
+    out = np.empty(n, dtype=np.uint8)
+    check(lib().sa_smp_mask_host(C.byref(smp), n, out.ctypes.data_as(C.c_void_p)), "sa_smp_mask_host")
     return out

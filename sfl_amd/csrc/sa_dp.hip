@@ -10,6 +10,7 @@
 #include "sa_elems.h"
 #include "sa_internal.h"
 #include "sa_philox.h"
+#include "sa_sumsq.h"
 
 namespace sa {
 
@@ -22,41 +23,12 @@ namespace sa {
 // grid depends on n only, so the partials, and the float64 sum, are the
 // same on every board and every run.
 using elems::f32x4;
-constexpr int kSumsqUnroll = 2;
 
-__device__ __forceinline__ double sq4(f32x4 v) {
-  return (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
-}
-
-__device__ __forceinline__ double block_sum256(double acc) {
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  __shared__ double w[4];
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return (w[0] + w[1]) + (w[2] + w[3]);
-}
-
+// the body is sa_sumsq.h's, with the loader that yields x[i]: sa_smp.hip runs
+// the same body over FedSMP's update
 __global__ void __launch_bounds__(256) k_sumsq_partial(const float* __restrict__ x, uint64_t n,
                                                        double* __restrict__ partials) {
-  double acc = 0.0;
-  const uint64_t n4 = n / 4;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + (kSumsqUnroll - 1) * stride < n4; i += kSumsqUnroll * stride) {
-    f32x4 v[kSumsqUnroll];
-#pragma unroll
-    for (int u = 0; u < kSumsqUnroll; u++) v[u] = __builtin_nontemporal_load(x4 + i + u * stride);
-#pragma unroll
-    for (int u = 0; u < kSumsqUnroll; u++) acc += sq4(v[u]);
-  }
-  for (; i < n4; i += stride) acc += sq4(__builtin_nontemporal_load(x4 + i));
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const double v = x[n4 * 4 + threadIdx.x];
-    acc += v * v;
-  }
-  const double b = block_sum256(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = b;
+  sumsq_partial(SumsqVector{x}, n, partials, blockDim.x);
 }
 
 // fixed-order sum of the partials (deterministic), then the layer's squared
@@ -163,6 +135,12 @@ __global__ void __launch_bounds__(256) k_dp_perturb(const DpArgs a) {
 
 using namespace sa;
 
+int sa::launch_sumsq_final(const double* partials, int grid, double* sumsq, int accumulate, void* stream) {
+  hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, grid, sumsq, accumulate);
+  SA_HIP_CHECK(hipGetLastError());
+  return SA_OK;
+}
+
 static bool dp_ok(const sa_dp* dp, const char* who) {
   if (dp_fields_ok(dp)) return true;
   sa_set_error("%s: bad sa_dp (sumsq set, num_updates > 0, counter0 %% 4 == 0 required)", who);
@@ -175,17 +153,10 @@ extern "C" int sa_sumsq_f32(const float* x, uint64_t n, double* partials, double
     sa_set_error("sa_sumsq_f32: bad arguments (x must be 16-byte aligned)");
     return SA_ERR_ARG;
   }
-  // the grid depends on n only (not on the device's occupancy): the same
-  // partials, so the same float64 sum, on every board
-  uint64_t want = (n / 4 + 255) / 256;
-  if (want < 1) want = 1;
-  const int grid = (int)(want < (uint64_t)SA_DP_PARTIALS ? want : (uint64_t)SA_DP_PARTIALS);
+  const int grid = sumsq_grid(n);
   hipLaunchKernelGGL(k_sumsq_partial, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, partials);
   SA_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, grid, sumsq,
-                     accumulate);
-  SA_HIP_CHECK(hipGetLastError());
-  return SA_OK;
+  return launch_sumsq_final(partials, grid, sumsq, accumulate, stream);
 }
 
 extern "C" int sa_dp_perturb_f32(const float* x, uint64_t n, const sa_dp* dp, float* out, void* stream) {

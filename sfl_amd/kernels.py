@@ -458,6 +458,69 @@ def mask_dp(x: torch.Tensor, out: torch.Tensor, streams: Sequence[tuple], dp: L.
 
 
 # ---------------------------------------------------------------------------
+# FedSMP (sa_smp_*): the keyed mask, the masked scaled update d, its clipping
+# norm, the fused upload and the unfused path's last step
+# ---------------------------------------------------------------------------
+def make_smp(key: int, counter0: int, threshold: int, divisor: float) -> L.SMP:
+    if counter0 % 4:
+        raise ValueError("counter0 must be a multiple of 4")
+    return L.SMP(int(key) & _M64, int(counter0), int(threshold), float(divisor))
+
+
+def _smp_operands(who: str, *ts: torch.Tensor) -> None:
+    _require_gpu(*ts)
+    if any(t.dtype != torch.float32 or t.numel() != ts[0].numel() for t in ts):
+        raise ValueError(f"{who}: float32 tensors of equal size")
+
+
+def smp_mask(smp: L.SMP, out: torch.Tensor) -> torch.Tensor:
+    """out (uint8) = 1 where the element is kept (sa_smp_mask)."""
+    _require_gpu(out)
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("smp_mask: a contiguous uint8 out")
+    L.check(L.lib().sa_smp_mask(C.byref(smp), out.numel(), _ptr(out), C.c_void_p(_stream(out))), "sa_smp_mask")
+    return out
+
+
+def smp_delta(w0: torch.Tensor, w1: torch.Tensor, smp: L.SMP, out: torch.Tensor) -> torch.Tensor:
+    """out = kept ? (w1 - w0) / divisor : 0 (sa_smp_delta_f32)."""
+    _smp_operands("smp_delta", w0, w1, out)
+    L.check(L.lib().sa_smp_delta_f32(_ptr(w0), _ptr(w1), w0.numel(), C.byref(smp), _ptr(out),
+                                     C.c_void_p(_stream(out))), "sa_smp_delta_f32")
+    return out
+
+
+def smp_sumsq(w0: torch.Tensor, w1: torch.Tensor, smp: L.SMP, out: torch.Tensor, partials: torch.Tensor, *,
+              accumulate: bool = False) -> torch.Tensor:
+    """out[0] (+)= sumsq_f32 of smp_delta's output, without storing it (sa_smp_sumsq_f32)."""
+    _smp_operands("smp_sumsq", w0, w1)
+    _require_gpu(out, partials)
+    if out.dtype != torch.float64 or partials.dtype != torch.float64 or partials.numel() < L.SA_DP_PARTIALS:
+        raise ValueError("smp_sumsq: float64 out, SA_DP_PARTIALS float64 partials")
+    L.check(L.lib().sa_smp_sumsq_f32(_ptr(w0), _ptr(w1), w0.numel(), C.byref(smp), _ptr(partials), _ptr(out),
+                                     int(bool(accumulate)), C.c_void_p(_stream(out))), "sa_smp_sumsq_f32")
+    return out
+
+
+def smp_perturb(w0: torch.Tensor, w1: torch.Tensor, smp: L.SMP, dp: L.DP | None, out: torch.Tensor) -> torch.Tensor:
+    """out = kept ? w0 + (clip + noise of d) : w0 in one pass; ``dp`` None: no clip, no noise
+    (sa_smp_perturb_f32).  out may be w1."""
+    _smp_operands("smp_perturb", w0, w1, out)
+    L.check(L.lib().sa_smp_perturb_f32(_ptr(w0), _ptr(w1), w0.numel(), C.byref(smp),
+                                       None if dp is None else C.byref(dp), _ptr(out), C.c_void_p(_stream(out))),
+            "sa_smp_perturb_f32")
+    return out
+
+
+def smp_finish(w0: torch.Tensor, t: torch.Tensor, smp: L.SMP, out: torch.Tensor) -> torch.Tensor:
+    """out = kept ? w0 + t : w0 (sa_smp_finish_f32).  out may be t."""
+    _smp_operands("smp_finish", w0, t, out)
+    L.check(L.lib().sa_smp_finish_f32(_ptr(w0), _ptr(t), w0.numel(), C.byref(smp), _ptr(out),
+                                      C.c_void_p(_stream(out))), "sa_smp_finish_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # GaussianModelDP with ChaCha20 noise (sa_dp_perturb_secure_f32 and the two
 # halves it is made of: sa_chacha20_keystream, sa_hb_normals_f64).  uint32
 # words are carried as ``torch.int32`` tensors (same bits).

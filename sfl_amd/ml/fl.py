@@ -27,7 +27,9 @@ Reference interfaces followed:
 Parties are ``PYU``s (``sfl_amd.device``); local training runs on
 ``train_device`` (the party's GPU by default, or the CPU).  Out of scope:
 the reference's dataset builders, callbacks, DP accountant hooks and the
-other strategies (fed_prox, scaffold, ...);
+other strategies (fed_prox, scaffold, ...); ``fed_smp`` (sparsified model
+perturbation, ``examples/security/h_gia/FedSMP_defense/FedSMP_torch.py``) is
+mirrored at the end of this text;
 ``moon`` is mirrored because its reference test is the FL end-to-end the
 survey names for the aggregator swap, ``fed_avg_u``
 and ``fed_avg_g`` because they are the other payload producers of §8(a8)
@@ -48,6 +50,17 @@ an aggregator that takes them, ``SparsePlainAggregator``.  ``fed_scr`` (structur
 the upload, ``fed_scr.py:42-139``; the server passes it through,
 ``compress.py:56-57``) is the reference's other compression strategy and
 shares ``fed_stc``'s worker flow; its kernels are ``sa_scr``'s.
+
+``fed_smp`` is the reference's strategy that combines sparsification with
+client-level DP, the scheme whose output feeds the secure aggregator: the
+server draws a random mask each round, a worker masks and rescales its
+update, clips and noises it with ``dp_strategy.model_gdp``, masks it again
+and uploads ``old + that`` (``FedSMP_torch.py:46-141``; the server's side,
+``FedSMP_server_agg_method.aggregate`` at ``:149-203``, is ``FLModel``'s
+here, with any aggregator).  The mask is keyed: the server sends ``(params,
+SMPMask(key, p))``, 16 bytes of mask instead of an int64 array of the
+model's shape, and the worker's step is ``sfl_amd.security.privacy.smp``'s
+(two streaming ``sa_smp`` passes per layer on a GPU model).
 """
 
 from __future__ import annotations
@@ -62,6 +75,7 @@ import torch
 
 from .. import hostpipe as H
 from ..device import PYU, PYUObject, reveal
+from ..security.privacy.smp import SMPMask, mask_key, smp_step
 from ..utils.compressor import scr_step, stc_step
 from ..utils.sparse import SparseCOO, payload_nbytes, sparse_decode, sparse_encode
 
@@ -480,7 +494,63 @@ class FedSCR(FedSTC):
         return out
 
 
-_STRATEGIES = {("fed_stc", "torch"): FedSTC, ("fed_scr", "torch"): FedSCR, ("fed_avg_w", "torch"): FedAvgW, ("fed_avg_u", "torch"): FedAvgU, ("fed_avg_g", "torch"): FedAvgG,
+class FedSMP(FedAvgW):
+    """``fed_smp`` worker (examples/security/h_gia/FedSMP_defense/
+    FedSMP_torch.py:46-141): take the server's weights and mask, snapshot,
+    train, and upload ``old + mask * model_gdp(mask * (new - old) /
+    (compression_ratio + 1e-6))`` (``smp_step``; its docstring has the
+    definition and where it departs from the reference).
+
+    The server's message is ``(weights, SMPMask)``; ``compression_ratio`` is
+    the keep probability the server draws its masks with (the divisor comes
+    from the mask received, which carries the same ratio).  ``smp_device``
+    says where the step runs (default: the training device).  With a GPU
+    model the weights, the snapshot and the upload stay on the device; with
+    a host model and a GPU ``smp_device`` the float32 layers cross through
+    pinned memory (``hostpipe.h2d`` / ``d2h``)."""
+
+    def __init__(self, builder: TorchModel, device: PYU, random_seed: Optional[int] = None,
+                 train_device: Optional[torch.device] = None, compression_ratio: float = 1.0, smp_device=None,
+                 **kwargs):
+        super().__init__(builder, device, random_seed, train_device)
+        assert 0 <= compression_ratio <= 1, f"compression ratio should between 0 and 1, but get {compression_ratio}"
+        self.compression_ratio = float(compression_ratio)
+        self.smp_device = torch.device(smp_device) if smp_device is not None else self.exe_device
+        self._resident = self.exe_device.type != "cpu" and self.smp_device == self.exe_device
+        self.grad_mask: Optional[SMPMask] = None
+
+    def _state(self) -> list:
+        if self._resident:
+            return [v.detach().clone() for v in self.model.state_dict().values()]
+        return self.get_weights()
+
+    def set_weights(self, weights, model: Optional[torch.nn.Module] = None):
+        if isinstance(weights, tuple) and len(weights) == 2 and isinstance(weights[1], SMPMask):  # :125-127
+            weights, self.grad_mask = weights
+        super().set_weights(weights, model)
+
+    def _smp(self, old: list, new: list, model_gdp) -> list:
+        if self._resident or self.smp_device.type == "cpu":
+            return smp_step(old, new, self.grad_mask, model_gdp)
+        dev, f32 = self.smp_device, [a.dtype == np.float32 for a in old]
+        up = smp_step([H.h2d(a, dev) if f else a for a, f in zip(old, f32)],
+                      [H.h2d(a, dev) if f else a for a, f in zip(new, f32)], self.grad_mask, model_gdp)
+        return [H.d2h(a, pooled=False) if f else a for a, f in zip(up, f32)]
+
+    def train_step(self, weights, cur_steps: int, train_steps: int, refresh_data: bool = False,
+                   dp_strategy=None, **kwargs):
+        self._begin_step(refresh_data)
+        if weights is not None:  # :68-75
+            self.set_weights(weights)
+        if self.grad_mask is None:
+            raise ValueError("fed_smp: no mask received yet; the server sends (weights, SMPMask)")
+        old = self._state()  # :78
+        num_sample = self._train(train_steps)
+        model_gdp = dp_strategy.model_gdp if dp_strategy is not None else None
+        return self._smp(old, self._state(), model_gdp), num_sample  # :105-119
+
+
+_STRATEGIES = {("fed_smp", "torch"): FedSMP, ("fed_stc", "torch"): FedSTC, ("fed_scr", "torch"): FedSCR, ("fed_avg_w", "torch"): FedAvgW, ("fed_avg_u", "torch"): FedAvgU, ("fed_avg_g", "torch"): FedAvgG,
                ("moon", "torch"): MOON}
 
 
@@ -496,7 +566,16 @@ class FLModel:
     ``accepts_sparse`` (``SparsePlainAggregator``).  When it is set,
     ``history`` has ``upload_bytes`` and ``download_bytes``, one entry per
     round: the bytes of all parties' uploads and of all parties' copies of
-    the downstream payload."""
+    the downstream payload.
+
+    ``strategy="fed_smp"`` (``compression_ratio``, ``smp_device``): after the
+    initial average and after every aggregation the server draws a fresh mask
+    key and sends ``(params, SMPMask(key, compression_ratio))`` to every
+    party.  Without a ``random_seed`` the key is ``secrets.randbits(64)``;
+    with one, draw ``k`` (0 with the initial average) has the key
+    ``sfl_amd.security.privacy.smp.mask_key(random_seed, k)``.  ``masks``
+    keeps the masks drawn so far and ``history["mask_bytes"]`` the bytes of
+    mask sent per round, 16 per party."""
 
     def __init__(self, server: Optional[PYU] = None, device_list: List[PYU] = (), model: TorchModel = None,
                  aggregator=None, strategy: str = "fed_avg_w", backend: str = "torch",
@@ -523,6 +602,9 @@ class FLModel:
         self._aggregator = aggregator
         self.strategy = strategy
         self.dp_strategy = dp_strategy
+        self._random_seed = random_seed
+        self._smp_ratio = float(kwargs.get("compression_ratio", 1.0))  # fed_smp: the masks' keep probability
+        self.masks: List[SMPMask] = []  # fed_smp: every mask drawn, in order
         self._sparsity = float(kwargs.get("sparsity", 0.0))  # fed_stc: the server compresses at the same rate
         self._res: list = []  # fed_stc: the server's residual (fl_model.py:544-556)
         self._workers: Dict[PYU, FedAvgW] = {
@@ -536,9 +618,19 @@ class FLModel:
         every pair's mask streams by the model's parameter count."""
         ws = [PYUObject(d, w.get_weights()) for d, w in self._workers.items()]
         init = self._aggregator.average(ws, axis=0)
+        down = self._with_mask(init)
         for d, w in self._workers.items():
-            w.set_weights(reveal(init.to(d)))
+            w.set_weights(reveal(down.to(d)))
         return init
+
+    def _with_mask(self, model_params: PYUObject) -> PYUObject:
+        """What the server sends down: for ``fed_smp`` the aggregate with a
+        freshly drawn mask (FedSMP_torch.py:201-203, the mask as its key and
+        ratio), for every other strategy the aggregate itself."""
+        if self.strategy != "fed_smp":
+            return model_params
+        self.masks.append(SMPMask(mask_key(self._random_seed, len(self.masks)), self._smp_ratio))
+        return PYUObject(model_params.device, (model_params.data, self.masks[-1]))
 
     def _server_stc(self, agg_data: list):
         """The ``fed_stc`` server step (fl_model.py:542-556, compress.py:28-42):
@@ -577,6 +669,8 @@ class FLModel:
                    "init_s": 0.0, "eval_s": 0.0}
         if self.sparse_transport is not None:
             history["upload_bytes"], history["download_bytes"] = [], []
+        if self.strategy == "fed_smp":
+            history["mask_bytes"] = []
         # reference fit (fl_model.py:473): the initial weights are averaged
         # through the aggregator before the first epoch
         t_init = time.perf_counter()
@@ -613,6 +707,9 @@ class FLModel:
                     model_params = PYUObject(model_params.device, down)
                 if self.sparse_transport is not None:
                     history["download_bytes"].append(len(self.device_list) * payload_nbytes(reveal(model_params)))
+                model_params = self._with_mask(model_params)
+                if self.strategy == "fed_smp":
+                    history["mask_bytes"].append(len(self.device_list) * SMPMask.nbytes)
                 model_params_list = [model_params.to(d) for d in self.device_list]
                 history["round_s"].append(time.perf_counter() - t_round)
                 if round_hook is not None:
