@@ -17,7 +17,7 @@ MI355X: ~57 GB/s each way, ~79 GB/s both ways at once), not the kernels (a
   fresh arrays beside registered memory failed now and then with
   hipErrorInvalidValue, once aborting in the next synchronise, and once
   with an illegal address: ``d2h`` / ``h2d`` serve the one-shot paths);
-* the result goes into a recycled registered buffer (``ResultPool``: free
+* the result goes into a recycled page-locked buffer (``ResultPool``: free
   once the caller dropped every array viewing it), so its D2H is async DMA
   into pages that are in; on a miss, chunk j lands in a pinned slot and a
   drain thread copies it into a fresh ``np.empty`` (faulting its pages on
@@ -41,6 +41,7 @@ import queue
 import sys
 import threading
 import time
+import weakref
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -107,10 +108,10 @@ def host_dtype(t):
 
 def d2h(t, pooled: bool = True) -> np.ndarray:
     """A device tensor's elements in a new host array without a pageable
-    DMA (a large pageable copy beside registered memory -- ``RESULTS``,
+    DMA (a large pageable copy beside page-locked memory -- ``RESULTS``,
     ``Pinned`` -- failed now and then with hipErrorInvalidValue or an
     illegal address; every host copy of the one-shot paths goes through
-    here): straight into a recycled registered buffer when ``pooled`` and
+    here): straight into a recycled page-locked buffer when ``pooled`` and
     one is free, else into a pinned buffer and out of it on the pool's
     threads.  Blocking."""
     import torch
@@ -135,7 +136,7 @@ def d2h(t, pooled: bool = True) -> np.ndarray:
 def h2d(a, dev):
     """A host array (numpy or a CPU tensor) as a new tensor on ``dev``,
     without a pageable DMA (``d2h``): an array inside a pooled result is
-    copied as it is (registered), anything else through a pinned buffer
+    copied as it is (page-locked), anything else through a pinned buffer
     filled on the pool's threads.  Ordered on ``dev``'s current stream."""
     import torch
 
@@ -221,7 +222,7 @@ def _np(t, dtype) -> np.ndarray:
 
 class FreshOutput:
     """A host result of ``n`` elements that the device fills chunk by chunk.
-    A recycled registered buffer from ``RESULTS`` when one is free: chunk
+    A recycled page-locked buffer from ``RESULTS`` when one is free: chunk
     j's D2H is async DMA straight into it.  Otherwise a fresh ``np.empty``
     (numpy advises huge pages for large allocations: first touch ~27 GB/s a
     thread against ~8 GB/s for a plain anonymous mmap, tools/touch_probe.py)
@@ -236,7 +237,7 @@ class FreshOutput:
         self.stats = {"pooled": False, "drain_ms": 0.0}
         self._q = self._thread = self._error = None
         owner = RESULTS.take(n * dtype.itemsize)
-        if owner is not None:  # a recycled, registered buffer: no faults, async DMA
+        if owner is not None:  # a recycled, page-locked buffer: no faults, async DMA
             self.array = owner[:n * dtype.itemsize].view(dtype)
             self.stats["pooled"] = True
             return
@@ -295,18 +296,33 @@ class FreshOutput:
                 raise self._error
 
 
+def pinned_bytes(nbytes: int):
+    """``nbytes`` of page-locked host memory of our own (hipHostMalloc) as a
+    uint8 array, freed when the array and every view of it are gone; None
+    when the driver has none to give.  Allocated page-locked, not registered
+    afterwards: a driver that refuses to lock pages a process already has (a
+    virtual machine's) still hands these out."""
+    hip, p = _hip(), ctypes.c_void_p()
+    if hip.hipHostMalloc(ctypes.byref(p), ctypes.c_size_t(nbytes), ctypes.c_uint(0)) or not p.value:
+        hip.hipGetLastError()  # clear the refused call's error state
+        return None
+    owner = np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p.value), dtype=np.uint8)
+    # every numpy view of ``owner`` holds it; not at exit: the runtime may be gone by then
+    weakref.finalize(owner, hip.hipHostFree, p).atexit = False
+    return owner
+
+
 class ResultPool:
-    """Registered host buffers for the pipelined results, recycled once the
+    """Page-locked host buffers for the pipelined results, recycled once the
     caller has dropped every array that views them: a per-party masked
     vector is shipped and dropped every round, so from the second round on
-    its D2H lands in registered pages without a fault (the fresh-result path
+    its D2H lands in locked pages without a fault (the fresh-result path
     pays ~6 ms of page faults and a pageable copy per 800 MB).  A buffer is
     free when nothing but the pool references it (``sys.getrefcount``: every
     numpy view of it holds its owner).  New buffers are made on a miss while
     the pool holds less than ``cap`` bytes (SFL_HOSTPIPE_POOL_BYTES, default
-    8 GiB; 0 disables), at the cost of one fresh result (parallel first
-    touch, then one registration); beyond the cap, results are fresh arrays
-    again."""
+    8 GiB; 0 disables), at the cost of one page-locked allocation
+    (``pinned_bytes``); beyond the cap, results are fresh arrays again."""
 
     def __init__(self, cap: int):
         self.cap = cap
@@ -326,36 +342,21 @@ class ResultPool:
                 return self.bufs[best]
             if sum(b.nbytes for b in self.bufs) + nbytes > self.cap:
                 return None
-            owner = np.empty(nbytes, dtype=np.uint8)
-            step = -(-nbytes // COPY_THREADS) // PAGE * PAGE + PAGE
-
-            def touch(lo):
-                owner[lo:lo + step:PAGE] = 0
-
-            list(_pool().map(touch, range(0, nbytes, step)))
-            hip = _hip()
-            if hip.hipHostRegister(ctypes.c_void_p(owner.ctypes.data), ctypes.c_size_t(nbytes), ctypes.c_uint(0)):
-                hip.hipGetLastError()
-                return None
-            self.bufs.append(owner)
+            owner = pinned_bytes(nbytes)
+            if owner is not None:
+                self.bufs.append(owner)
             return owner
 
     def contains(self, a: np.ndarray) -> bool:
-        """``a``'s memory lies inside one of the pool's (registered) buffers."""
+        """``a``'s memory lies inside one of the pool's (page-locked) buffers."""
         p0, p1 = a.ctypes.data, a.ctypes.data + a.nbytes
         with self.lock:
             return any(b.ctypes.data <= p0 and p1 <= b.ctypes.data + b.nbytes for b in self.bufs)
 
     def clear(self) -> None:
-        """Unregister and drop every free buffer (tests, memory pressure)."""
+        """Drop (and so free) every free buffer (tests, memory pressure)."""
         with self.lock:
-            keep = []
-            for i in range(len(self.bufs)):
-                if sys.getrefcount(self.bufs[i]) == 2:
-                    _hip().hipHostUnregister(ctypes.c_void_p(self.bufs[i].ctypes.data))
-                else:
-                    keep.append(self.bufs[i])
-            self.bufs = keep
+            self.bufs = [self.bufs[i] for i in range(len(self.bufs)) if sys.getrefcount(self.bufs[i]) != 2]
 
 
 RESULTS = ResultPool(int(os.environ.get("SFL_HOSTPIPE_POOL_BYTES", str(8 << 30))))
@@ -509,11 +510,12 @@ class Pinned:
     touch these pages while they are registered, and none of them is
     pageable.  Arrays inside a pooled result (``RESULTS``: e.g. the masked
     vectors the server receives from parties in the same process) are
-    registered already and taken as they are; with ``register=False``
+    page-locked already and taken as they are; with ``register=False``
     nothing else is registered (``ok`` then says whether every array was
     pooled).  ``ok`` is False when the driver refuses an array registered
-    on entry (already registered elsewhere, or sharing a page with
-    registered memory): nothing stays registered and the caller stages
+    on entry (already registered elsewhere, sharing a page with registered
+    memory, or any at all under a virtual machine's driver): nothing stays
+    registered and the caller stages
     through the feeder.  Unregistered on exit.
 
     Arrays of ``LAZY_MIN_BYTES`` or more are registered lazily: nothing
@@ -550,16 +552,16 @@ class Pinned:
 
     def __enter__(self):
         for a in self.arrays:
-            if RESULTS.contains(a):  # one of our pooled results: registered already
+            if RESULTS.contains(a):  # one of our pooled results: page-locked already
                 continue
             if not self.register:
-                self.__exit__(None, None, None)
+                self._unregister()
                 return self
             p0, p1 = a.ctypes.data, a.ctypes.data + a.nbytes
             if a.nbytes >= LAZY_MIN_BYTES:
                 self.spans.append(_Span(p0, p1))
             elif not self._reg(p0, p1):
-                self.__exit__(None, None, None)
+                self._unregister()
                 return self
         self.spans.sort(key=lambda sp: sp.start)
         self._keys = [sp.start for sp in self.spans]
@@ -601,11 +603,14 @@ class Pinned:
             self.stats["staged_bytes"] += p1 - cur
         return out
 
-    def __exit__(self, *exc):
+    def _unregister(self) -> None:
         hip = _hip()
         while self.done:
             hip.hipHostUnregister(ctypes.c_void_p(self.done.pop()))
         self.spans, self._keys = [], []
+
+    def __exit__(self, *exc):
+        self._unregister()
         return False
 
 

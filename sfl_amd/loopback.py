@@ -21,12 +21,12 @@ star): the per-round rate here includes H2D, D2H and the loopback copies.
 The GPU kernels are the product path; nothing here falls back to the CPU.
 
 Host buffers that leave through a socket (every client's masked vector, the
-server's float64 result) are ``SharedHostBuffer``s: memfd-backed pages that
-are HIP-registered, so the D2H copy lands in them directly.  They are sent
-with ``sendall`` (a copy into the kernel): ``sendfile`` from the memfd pages
-has no send-side copy, but measured no faster at 8 x 100M and 26 % slower at
-32 x 256M (DESIGN.md §7, profiles/r03/loopback_*_ab.jsonl;
-tools/socket_floor.py for the transport alone).  Clients receive the result
+server's float64 result) are ``SharedHostBuffer``s: page-locked pages of our
+own, so the D2H copy lands in them directly.  They are sent with ``sendall``
+(a copy into the kernel): ``sendfile`` from memfd pages has no send-side
+copy, but measured no faster at 8 x 100M and 26 % slower at 32 x 256M
+(profiles/r03/loopback_*_ab.jsonl; tools/socket_floor.py for
+the transport alone).  Clients receive the result
 while they send (``LoopbackClient.submit`` says why), and GPU waits poll
 instead of spinning a core.
 """
@@ -88,44 +88,18 @@ def wait_event(e) -> None:
         time.sleep(50e-6)
 
 
-_HIP = None
-
-
-def _hip():
-    global _HIP
-    if _HIP is None:
-        import ctypes
-
-        _HIP = ctypes.CDLL("libamdhip64.so")
-    return _HIP
-
-
 class SharedHostBuffer:
-    """``nbytes`` of memfd-backed host memory, mapped, faulted in and
-    HIP-registered (hipHostRegister): device copies land in it directly (torch
-    sees it as pinned), and ``send(sock, lo, hi)`` ships a byte range with
-    ``sendall``."""
+    """``nbytes`` of page-locked host memory of our own
+    (``hostpipe.pinned_bytes``: hipHostMalloc) as ``array``: device copies
+    land in it directly (torch sees it as pinned), and ``send(sock, lo, hi)``
+    ships a byte range with ``sendall``."""
 
     def __init__(self, nbytes: int, dtype=np.float64):
-        import ctypes
-        import mmap
-
         self.nbytes = max(int(nbytes), 8)
-        self.fd = os.memfd_create("sfl_sa_wire", os.MFD_CLOEXEC)
-        try:
-            os.ftruncate(self.fd, self.nbytes)
-            self._mm = mmap.mmap(self.fd, self.nbytes)
-        except BaseException:
-            os.close(self.fd)
-            raise
-        self.array = np.frombuffer(self._mm, dtype=dtype)
-        self.array.view(np.uint8)[:] = 0  # fault every page in before registering
-        self._ptr = self.array.ctypes.data
-        rc = _hip().hipHostRegister(ctypes.c_void_p(self._ptr), ctypes.c_size_t(self.nbytes), ctypes.c_uint(0))
-        if rc != 0:
-            self._close_map()
-            raise RuntimeError(f"hipHostRegister of a {self.nbytes}-byte memfd buffer failed (hipError {rc})")
-        self._registered = True
+        owner = H.pinned_bytes(self.nbytes)
+        if owner is None:
+            raise RuntimeError(f"no page-locked host buffer of {self.nbytes} bytes (hipHostMalloc failed)")
+        self.array = owner.view(dtype)
 
     def tensor(self):
         import torch
@@ -137,29 +111,9 @@ class SharedHostBuffer:
         if hi > lo:
             sock.sendall(memoryview(self.array).cast("B")[lo:hi])
 
-    def _close_map(self):
-        self.array = None
-        try:
-            self._mm.close()
-        except BufferError:  # a view of the pages is still alive: the mapping goes with it
-            pass
-        os.close(self.fd)
-        self.fd = -1
-
     def close(self):
-        if getattr(self, "_registered", False):
-            import ctypes
-
-            _hip().hipHostUnregister(ctypes.c_void_p(self._ptr))
-            self._registered = False
-        if getattr(self, "fd", -1) >= 0:
-            self._close_map()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+        """Give the pages up: they are freed once no view of them is alive."""
+        self.array = None
 
 
 def chunk_elems() -> int:
@@ -211,13 +165,13 @@ class LoopbackServer:
         if self._bufs is None or self._bufs[0] != n:
             dev = torch.device("cuda", self.gpu)
             ce = min(n, chunk_elems())
-            if self._bufs is not None:  # the old result pages (8n bytes, HIP-registered) go now, not at GC
+            if self._bufs is not None:  # the old result pages (8n bytes, page-locked) go now, not at GC
                 self._bufs[4][2].close()
                 self._bufs = None
             ring = [[torch.empty(ce, dtype=torch.int64).pin_memory() for _ in range(2)] for _ in self.conns]
             devb = [torch.empty(n, dtype=torch.int64, device=dev) for _ in self.conns]
             streams = [torch.cuda.Stream(dev) for _ in self.conns]
-            # the float64 result: D2H straight into the registered pages the broadcast sends
+            # the float64 result: D2H straight into the page-locked pages the broadcast sends
             agg = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
                    SharedHostBuffer(8 * n, np.float64), torch.cuda.Stream(dev))
             self._bufs = (n, ring, devb, streams, agg)
@@ -447,7 +401,7 @@ class LoopbackClient:
             ce = min(n, chunk_elems())
             if self._bufs is not None:
                 self._bufs[2].close()
-            # the masked vector: D2H straight into registered pages, sent chunk by chunk
+            # the masked vector: D2H straight into page-locked pages, sent chunk by chunk
             self._bufs = (n, [torch.empty(ce, dtype=torch.float32).pin_memory() for _ in range(2)],
                           SharedHostBuffer(8 * n, np.int64),
                           torch.empty(n, dtype=torch.float32, device=dev),
@@ -483,7 +437,7 @@ class LoopbackClient:
         ``GaussianModelDP`` ``dp``, its clip + noise runs inside the masking
         kernel (``sa_mask_dp``) on the device copy of ``x``.  ``x`` streams to
         the device through two pinned chunk buffers; the masked vector comes
-        back chunk by chunk into registered memfd pages, each chunk sent as it
+        back chunk by chunk into page-locked pages, each chunk sent as it
         lands.
 
         ``result_into`` (float64, n elements; or a list of two float64 chunk

@@ -2,10 +2,13 @@
 buffers, like the product, so no test adds a pageable DMA to a process that
 may hold registered host memory (DESIGN.md sections 7 and 13).  GPU tests move
 arrays only through these helpers; tests/test_gpu_copies_rule.py keeps it so."""
+import functools
+
 import numpy as np
 import torch
 
 DEV = "cuda:0"
+NO_REGISTER = "hipHostRegister is not supported here"
 
 
 def _bits(x):
@@ -42,3 +45,24 @@ def _u64(t):
 def _item(t):
     """The Python value of a one-element device tensor."""
     return _host(t).item()
+
+
+@functools.lru_cache(maxsize=None)
+def registers_host_memory():
+    """Whether the driver page-locks memory the process already has
+    (hipHostRegister; a virtual machine's refuses every call), asked once on
+    two pages of our own.  The tests whose subject is that registration skip
+    themselves with ``NO_REGISTER`` where it does not."""
+    import ctypes
+
+    from sfl_amd import hostpipe as H
+
+    torch.cuda.init()
+    hip = H._hip()
+    raw = np.zeros(3 * H.PAGE, dtype=np.uint8)
+    p = ctypes.c_void_p(raw.ctypes.data + -raw.ctypes.data % H.PAGE)
+    if hip.hipHostRegister(p, ctypes.c_size_t(2 * H.PAGE), ctypes.c_uint(0)):
+        hip.hipGetLastError()  # clear the refused call's error state
+        return False
+    hip.hipHostUnregister(p)
+    return True

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from gpu_copies import _dev  # noqa: E402
+from gpu_copies import NO_REGISTER, _dev, registers_host_memory  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -187,6 +187,8 @@ def test_run_chunks_round_trip(pinned, layers, monkeypatch):
 
     from sfl_amd import hostpipe as H
 
+    if pinned and not registers_host_memory():
+        pytest.skip(NO_REGISTER)
     layers, want = layers
     if not pinned:
         monkeypatch.setattr(H, "Pinned", _NotPinned)

@@ -98,8 +98,8 @@ def test_loopback_client_reproduces_numpy_rejection():
 
 
 def test_loopback_chunks_without_result_copies(monkeypatch):
-    """Many chunks (masked vectors D2H into registered
-    memfd pages chunk by chunk, each sent as it lands; the result D2H'd into
+    """Many chunks (masked vectors D2H into page-locked
+    pages chunk by chunk, each sent as it lands; the result D2H'd into
     the server's pages and broadcast from them), with no copy of the result
     kept by the server or the clients (keep_results=False: the clients
     receive it through a ring of two chunks and checksum it as it lands):

@@ -16,7 +16,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from gpu_copies import _dev, _u64  # noqa: E402
+from gpu_copies import NO_REGISTER, _dev, _u64, registers_host_memory  # noqa: E402
 from oracle import secagg as o  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -390,6 +390,8 @@ def test_lazy_registration_bit_exact(growth, refuse_after, monkeypatch):
     from sfl_amd.security.aggregation import SecureAggregator
     from sfl_amd.security.aggregation import party as P
 
+    if not registers_host_memory():
+        pytest.skip(NO_REGISTER)
     monkeypatch.setattr(H, "LAZY_MIN_BYTES", 1 << 20)
     monkeypatch.setattr(H, "LAZY_GROWTH", growth)
     stats = []

@@ -46,10 +46,23 @@ def test_host_layers_keep_contiguous_memory():
 
 
 class _FakeHip:
-    """hipHostRegister / Unregister stand-ins (no GPU here)."""
+    """hipHostMalloc / Free and hipHostRegister / Unregister stand-ins (no
+    GPU here): ``live`` holds what is allocated or registered."""
 
     def __init__(self):
-        self.live = set()
+        self.live, self.mem = set(), {}
+
+    def hipHostMalloc(self, ref, n, f):
+        buf = np.empty(n.value, np.uint8)
+        self.mem[buf.ctypes.data] = buf
+        self.live.add(buf.ctypes.data)
+        ref._obj.value = buf.ctypes.data
+        return 0
+
+    def hipHostFree(self, p):
+        self.live.discard(p.value)
+        del self.mem[p.value]
+        return 0
 
     def hipHostRegister(self, p, n, f):
         self.live.add(p.value)

@@ -1,10 +1,8 @@
 """The loopback runtime's send path (sfl_amd.loopback.SharedHostBuffer) on
 the CPU: byte ranges sent over a socket with a
 timeout (a non-blocking descriptor) whose buffer fills while the receiver
-sleeps -- every byte arrives, in order, in several ranges.  (HIP registration
-of the pages is exercised on the GPU by tests/test_gpu_loopback.py.)"""
-import mmap
-import os
+sleeps -- every byte arrives, in order, in several ranges.  (Page-locked
+pages are exercised on the GPU by tests/test_gpu_loopback.py.)"""
 import socket
 import threading
 import time
@@ -15,20 +13,15 @@ import pytest
 from sfl_amd import loopback as lb
 
 
-class _Unregistered(lb.SharedHostBuffer):
-    def __init__(self, nbytes):  # the memfd part only: no GPU here
+class _Pageable(lb.SharedHostBuffer):
+    def __init__(self, nbytes):  # ordinary pages: no GPU to lock them here
         self.nbytes = nbytes
-        self.fd = os.memfd_create("sfl_test")
-        os.ftruncate(self.fd, nbytes)
-        self._mm = mmap.mmap(self.fd, nbytes)
-        self.array = np.frombuffer(self._mm, dtype=np.uint8)
-        self.array[:] = np.arange(nbytes) % 251
-        self._registered = False
+        self.array = (np.arange(nbytes) % 251).astype(np.uint8)
 
 
 def test_send_ranges_through_a_full_socket_buffer():
     n = 96 << 20
-    buf = _Unregistered(n)
+    buf = _Pageable(n)
     srv = socket.create_server(("127.0.0.1", 0))
     got = bytearray(n)
 
@@ -55,7 +48,7 @@ def test_send_ranges_through_a_full_socket_buffer():
     srv.close()
     assert bytes(got) == bytes(buf.array)
     buf.close()
-    assert buf.fd == -1
+    assert buf.array is None
 
 
 def test_placement_one_process_per_gpu():
