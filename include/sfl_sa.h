@@ -965,6 +965,63 @@ int sa_smp_perturb_f32(const float* w0, const float* w1, uint64_t n, const sa_sm
  * any model-level DP): the last step of the unfused path; out may alias t */
 int sa_smp_finish_f32(const float* w0, const float* t, uint64_t n, const sa_smp* smp, float* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* pack=2: two 32-bit fixed-point values per 64-bit ring word           */
+/* ------------------------------------------------------------------ */
+/* bit set in *flags by the packed launches, beside SA_FLAG_PRG_REJECT */
+#define SA_FLAG_PACK_RANGE 2u /* a packed launch (sa_mask_pack2,
+                                 sa_fused_clients_pack2) met a product
+                                 x*w*2^fxp that is NaN or not below 2^31 /
+                                 n_clients in magnitude: the packed sums could
+                                 overflow their 32-bit halves, the launch's
+                                 outputs are unspecified. */
+
+/* The same protocol over the same ring Z/2^64 and the same mask streams,
+ * with HALF the words: for n float32 elements, q_i = trunc(x_i*(w*2^fxp))
+ * (float32, sa_mask's fast path) and n_words = ceil(n / 2) words
+ *   W[j] = sext64(q_2j) + (sext64(q_2j+1) << 32)   (mod 2^64; q_n = 0),
+ * masked exactly as sa_mask masks its elements: each stream advances by
+ * n_words draws, the server sums words with sa_sum_u64, and a flagged raw 0
+ * (SA_FLAG_PRG_REJECT) is replayed on words with sa_pcg64_find_zero /
+ * sa_stream_shift.  Range rule: every product p_i = x_i*(w*2^fxp) must
+ * satisfy |p_i| < limit, the largest float32 not above 2^31 / n_clients
+ * (n_clients: every party of the aggregation), so that no per-element sum
+ * of honest clients leaves 32 bits; a NaN or larger product sets
+ * SA_FLAG_PACK_RANGE and the outputs are then unspecified (there is no
+ * 64-bit fallback inside the launch).  Whenever the rule holds,
+ * sa_decode_pack2 of the summed words equals sa_decode of the unpacked
+ * sum bit for bit.  float32 data, scalar weights, fxp_bits 0..30, x
+ * 16-byte aligned (16-B loads). */
+
+/* sa_mask for one client, packed: out_words[j] = W[j] + sum_k sign_k *
+ * m_k[j] (mod 2^64), n_words u64.  n_clients_total: the parties of the
+ * aggregation (the range rule's C).  n_streams 0..16 (one pass; more:
+ * SA_ERR_UNSUPPORTED).  sum_accum (n_words, += masked), digest (^= XOR of
+ * the masked words) and flags as for sa_mask. */
+int sa_mask_pack2(const float* x, uint64_t n, double weight, int fxp_bits, int n_clients_total,
+                  const sa_mask_stream* streams, int n_streams, uint64_t* out_words, uint64_t* sum_accum,
+                  uint64_t* digest, uint32_t* flags, void* stream);
+
+/* sa_fused_clients for 2..8 co-located clients (all the parties: the range
+ * rule's C is n_clients), packed, no cross streams: every internal pair
+ * stream expanded once over n_words draws; sum_out_words (n_words u64, =
+ * or += the masked sum), clients[c].masked_out (n_words u64 wire image)
+ * and digests as for sa_fused_clients.  Other client counts:
+ * SA_ERR_UNSUPPORTED. */
+int sa_fused_clients_pack2(const sa_local_client* clients, int n_clients, uint64_t n, int fxp_bits,
+                           const sa_pcg64* pair_gens, const int8_t* pair_sign, uint64_t* sum_out_words,
+                           int accumulate, uint64_t* digests, uint32_t* flags, void* stream);
+
+/* Server decode of summed packed words S (ceil(n/2) u64) into n float64:
+ *   lo = (int32)(uint32)S, hi = (int32)((uint32)(S >> 32) + (lo < 0))
+ * (the borrow the sign extension of the low halves took),
+ *   out[2j] = (double)lo / 2^fxp / divisor, out[2j+1] = (double)hi / ...
+ * (dropped when 2j+1 == n); IEEE division as sa_decode.  A 16-byte aligned
+ * out takes one 16-B store per word (its two doubles), other alignments
+ * two 8-B stores. */
+int sa_decode_pack2(const uint64_t* s_words, uint64_t n, int fxp_bits, double divisor, double* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ SA_ERR_RCCL = -4
 
 SA_F32, SA_F64, SA_I64 = 0, 1, 2
 SA_FLAG_PRG_REJECT = 1
+SA_FLAG_PACK_RANGE = 2
 SA_UNIQUE_ID_BYTES = 128
 SA_DP_PARTIALS = 1024
 SA_COO_BAD_RANGE, SA_COO_BAD_ORDER, SA_COO_BAD_COUNT = 1, 2, 4
@@ -50,6 +51,7 @@ EXPORTED = (
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
     "sa_smp_mask_host", "sa_smp_mask", "sa_smp_delta_f32", "sa_smp_sumsq_f32", "sa_smp_perturb_f32",
     "sa_smp_finish_f32",
+    "sa_mask_pack2", "sa_fused_clients_pack2", "sa_decode_pack2",
 )
 
 
@@ -134,6 +136,9 @@ def _declare(lib):
     lib.sa_sum_u64.argtypes = [P(C.c_void_p), i32, u64, vp, vp]
     lib.sa_decode.argtypes = [vp, u64, i32, dbl, vp, vp, vp]
     lib.sa_sum_f64.argtypes = [P(C.c_void_p), i32, u64, vp, vp]
+    lib.sa_mask_pack2.argtypes = [vp, u64, dbl, i32, i32, P(MaskStream), i32, vp, vp, vp, vp, vp]
+    lib.sa_fused_clients_pack2.argtypes = [P(LocalClient), i32, u64, i32, P(PCG64), P(C.c_int8), vp, i32, vp, vp, vp]
+    lib.sa_decode_pack2.argtypes = [vp, u64, i32, dbl, vp, vp]
     lib.sa_comm_unique_id.argtypes = [vp, i32]
     lib.sa_comm_init.argtypes = [P(C.c_void_p), vp, i32, i32, i32]
     lib.sa_comm_reduce_u64.argtypes = [vp, vp, vp, u64, i32, vp]

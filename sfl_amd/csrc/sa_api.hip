@@ -1,8 +1,10 @@
 // sa_api.hip — the occupancy cache, the masking reserve and the masking
 // entry points of libsfl_sa.so (see include/sfl_sa.h): sa_mask,
-// sa_fused_clients, sa_fused_bipartite.  The server kernels are in
+// sa_fused_clients, sa_fused_bipartite and the packed sa_mask_pack2,
+// sa_fused_clients_pack2.  The server kernels are in
 // sa_server.hip, the blocking host-array entries in sa_host_calls.hip.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -390,6 +392,111 @@ extern "C" int sa_fused_bipartite(const sa_local_client* clients, int x_type, ui
     return SA_ERR_UNSUPPORTED;
   }
   return fn(b.outputs(sum_out, accumulate ? 2 : 1, nullptr, flags), stream);
+}
+
+// ---------------------------------------------------------------------------
+// pack=2: two 32-bit fixed-point values per ring word (include/sfl_sa.h)
+// ---------------------------------------------------------------------------
+// the range rule's bound: the largest float32 not above 2^31 / parties
+static float pack2_limit(int parties) {
+  const double d = 2147483648.0 / (double)parties;
+  float f = (float)d;
+  if ((double)f > d) f = nextafterf(f, 0.0f);
+  return f;
+}
+
+// what both packed entries check of their scalars; false: error set
+static bool pack2_scalars_ok(const char* who, int fxp_bits, int parties) {
+  if (fxp_bits < 0 || fxp_bits > 30 || parties < 1) {
+    sa_set_error("%s: bad arguments (fxp_bits=%d, want 0..30; parties=%d)", who, fxp_bits, parties);
+    return false;
+  }
+  return true;
+}
+
+// a packed launch's base image: n input elements as ceil(n / 2) ring words
+static LaunchArgs pack2_args(uint64_t n, int fxp_bits, int parties) {
+  LaunchArgs b((n + 1) / 2, fxp_bits);
+  b.a.n_elems = n;
+  b.a.pack_limit = pack2_limit(parties);
+  return b;
+}
+
+extern "C" int sa_mask_pack2(const float* x, uint64_t n, double weight, int fxp_bits, int n_clients_total,
+                             const sa_mask_stream* streams, int n_streams, uint64_t* out_words,
+                             uint64_t* sum_accum, uint64_t* digest, uint32_t* flags, void* stream) {
+  if (!pack2_scalars_ok("sa_mask_pack2", fxp_bits, n_clients_total)) return SA_ERR_ARG;
+  if (n == 0 && n_streams >= 0) return SA_OK;  // nothing to touch
+  if (!x || !out_words || n_streams < 0 || (n_streams > 0 && !streams)) {
+    sa_set_error("sa_mask_pack2: bad arguments (x=%p out_words=%p n_streams=%d)", (const void*)x, (void*)out_words,
+                 n_streams);
+    return SA_ERR_ARG;
+  }
+  if (!aligned16(x) || !aligned16(out_words) || !aligned16(sum_accum)) {
+    sa_set_error("sa_mask_pack2: device buffers must be 16-byte aligned");
+    return SA_ERR_ARG;
+  }
+  if (n_streams > kMaskPass) {  // a further pass would need the continue mode the packed kernel lacks
+    sa_set_error("sa_mask_pack2: %d streams exceed the %d of one pass", n_streams, kMaskPass);
+    return SA_ERR_UNSUPPORTED;
+  }
+  LaunchArgs b = pack2_args(n, fxp_bits, n_clients_total);
+  b.client(0, x, nullptr, out_words, weight);
+  for (int j = 0; j < n_streams; j++)
+    if (!b.stream(j, streams[j].gen, streams[j].sign, 0)) {
+      sa_set_error("sa_mask_pack2: stream %d has sign %d (want +1/-1)", j, streams[j].sign);
+      return SA_ERR_ARG;
+    }
+  const LaunchFn fn = find_pack2_kernel(1, n_streams, kLean1);
+  if (!fn) {
+    sa_set_error("sa_mask_pack2: no kernel for %d streams", n_streams);
+    return SA_ERR_UNSUPPORTED;
+  }
+  return fn(b.outputs(sum_accum, 2, digest, flags), stream);
+}
+
+extern "C" int sa_fused_clients_pack2(const sa_local_client* clients, int n_clients, uint64_t n, int fxp_bits,
+                                      const sa_pcg64* pair_gens, const int8_t* pair_sign, uint64_t* sum_out_words,
+                                      int accumulate, uint64_t* digests, uint32_t* flags, void* stream) {
+  const int L = n_clients;
+  if (!pack2_scalars_ok("sa_fused_clients_pack2", fxp_bits, L)) return SA_ERR_ARG;
+  if (n == 0) return SA_OK;  // empty vectors
+  if (!clients || !sum_out_words || (L > 1 && (!pair_gens || !pair_sign))) {
+    sa_set_error("sa_fused_clients_pack2: bad arguments (n_clients=%d)", L);
+    return SA_ERR_ARG;
+  }
+  if (L < 2 || L > kMaxLocal) {
+    sa_set_error("sa_fused_clients_pack2: %d co-located clients (2..%d per launch)", L, kMaxLocal);
+    return SA_ERR_UNSUPPORTED;
+  }
+  if (!aligned16(sum_out_words)) {
+    sa_set_error("sa_fused_clients_pack2: sum_out_words must be 16-byte aligned");
+    return SA_ERR_ARG;
+  }
+  LaunchArgs b = pack2_args(n, fxp_bits, L);
+  bool any_out = digests != nullptr;
+  for (int c = 0; c < L; c++) {
+    if (!clients[c].x || !aligned16(clients[c].x) || ((uintptr_t)clients[c].masked_out & 7)) {
+      sa_set_error("sa_fused_clients_pack2: client %d x null or not 16-byte aligned, or masked_out not 8-byte aligned",
+                   c);
+      return SA_ERR_ARG;
+    }
+    any_out = any_out || clients[c].masked_out != nullptr;
+    b.client(c, clients[c].x, nullptr, clients[c].masked_out, clients[c].weight);
+  }
+  int p = 0;
+  for (int u = 0; u < L; u++)
+    for (int v = u + 1; v < L; v++, p++)
+      if (!b.stream(p, pair_gens[p], pair_sign[p], u, v)) {
+        sa_set_error("sa_fused_clients_pack2: pair %d sign %d", p, pair_sign[p]);
+        return SA_ERR_ARG;
+      }
+  const LaunchFn fn = find_pack2_kernel(L, 0, any_out ? 0 : kSumOnly);
+  if (!fn) {
+    sa_set_error("sa_fused_clients_pack2: no kernel for %d clients", L);
+    return SA_ERR_UNSUPPORTED;
+  }
+  return fn(b.outputs(sum_out_words, accumulate ? 2 : 1, digests, flags), stream);
 }
 
 extern "C" int sa_set_masking_reserve(int cus) {

@@ -36,6 +36,46 @@
 // constants are folded on the host into one per-client `bias`, and the XOR
 // with smask commutes with the XSL-RR rotation, so a signed draw costs the
 // same as an unsigned one.
+//
+// The packed variant (K & kPacked, float32 only).  The ring,
+// the mask streams and everything written above stay as they are; a ring
+// word now carries TWO 32-bit fixed-point values,
+//   W[j] = sext64(q_2j) + (sext64(q_2j+1) << 32)  (mod 2^64),
+// so a gradient element costs half a draw, half a sum word and half a wire
+// word.  The tile is still 512 ring WORDS and a lane still owns two of them
+// (the same prologue, tile jump, draw groups, sa_draw3.h blocks, zero-draw
+// masks and 16-B u64 stores): KArgs::n counts words for all of that.  What
+// differs is the quantizer around the draws:
+//   * a lane's two words are FOUR input elements, one 16-B buffer load per
+//     client at byte offset 8 * word (instead of the 8-B load), through a
+//     descriptor of n_elems * 4 bytes (KArgs::n_elems): the per-dword bounds
+//     check zero-fills the odd tail (q_n = 0) and a load that straddles the
+//     end, so the packed tile has no tail path either;
+//   * four products per client with the host-rounded scale ClientArg::ws,
+//     written as four scalar multiplies (packed_quantize), i.e. four
+//     v_mul_f32 -- by choice, not the two v_pk_mul_f32 the unpacked kernel's
+//     vector multiply yields: 2 VALU a client and tile more, against ~1,440
+//     for 28 streams' draws.  The packed instances' translation unit is also
+//     built with packed-fp32 arithmetic switched off (Makefile, PACK2_FLAGS),
+//     which only keeps the compiler from re-forming packed multiplies; it
+//     changes no multiply today but does change the register allocation
+//     (figures and the A/B of both builds: DESIGN.md §21);
+//   * the range vote: the v_maximum3_f32 chain over all L * 4 products,
+//     compared with KArgs::pack_limit (the largest float32 not above 2^31 /
+//     parties) instead of 2^31.  A wave with a product at or above it, or a
+//     NaN, remembers it in one VGPR and ORs SA_FLAG_PACK_RANGE into *flags at
+//     its end (one atomic per wave at most, as for SA_FLAG_PRG_REJECT).
+//     There is no exact int64 path: the values convert with v_cvt_i32_f32
+//     whatever the vote says, and a flagged launch's outputs are unspecified;
+//   * the sum-only finish adds a client's word as the existing
+//     v_mad_i64_i32 (q_even * +-1 + A, the sign extension for free) and ONE
+//     32-bit add / subtract of q_odd into the accumulator's high dword;
+//   * the digest / wire-image finish forms W0, W1 and hands them to the same
+//     finish() (bstore2_u64, digests and sum_mode unchanged).
+// Register budget: the four inputs a client and lane hold across the mask
+// expansion are 2 VGPRs per client more than the unpacked tile's
+// (clients_waves counts them); L = 8 stays at 2 waves per SIMD without VGPR
+// spills (228 / 240 VGPRs, wire-image / sum-only instance, as shipped).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -157,6 +197,18 @@ __device__ __forceinline__ Vec2<T> bload2(rsrc_t r, uint64_t i) {
   }
   return out;
 }
+// the four fp32 elements of ring words j, j+1 of a packed launch (j even:
+// one 16-B aligned load at byte 8 * j; dwords past the end read 0)
+struct Vec4f {
+  float v[4];
+};
+__device__ __forceinline__ Vec4f bload4_f32(rsrc_t r, uint64_t j) {
+  const auto u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(j * 8), 0, 0);
+  Vec4f out;
+#pragma unroll
+  for (int e = 0; e < 4; e++) out.v[e] = __builtin_bit_cast(float, (uint32_t)u[e]);
+  return out;
+}
 // u64 elements i, i+1 (the part past the end is dropped by the bounds check)
 __device__ __forceinline__ void bstore2_u64(rsrc_t r, uint64_t i, uint64_t v0, uint64_t v1) {
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
@@ -268,6 +320,41 @@ __device__ __forceinline__ uint64_t exact_q(const Vec2<XT> (&xv)[L], const Vec2<
   const bool has_wv = kGeneral && ka->c[c].wvec;
   const CT w = has_wv ? wv[kGeneral ? c : 0].v[k] : scalar_weight<CT>(ka->c[c].w);
   return quantize<XT, CT>(xv[c].v[k], w, qs);
+}
+
+// The packed tile's quantizer: q = (int32)(x * ws) for the lane's four
+// elements of every client (ws: the host-rounded w * 2^fxp, ClientArg::ws),
+// and the range vote over all L * 4 products -- the largest |p| through the
+// NaN-propagating v_maximum3_f32 chain of fast_products, compared with the
+// launch's limit.  Returns false when some lane of the wave holds a product
+// that is NaN or not below the limit (the caller flags the launch; the
+// conversions are made regardless).
+template <int L>
+__device__ __forceinline__ bool packed_quantize(const Vec4f (&xq)[L],
+                                                const __attribute__((address_space(4))) KArgs* ka, float limit,
+                                                int32_t (&q)[L][4]) {
+  float p[L * 4];
+#pragma unroll
+  for (int c = 0; c < L; c++) {
+    const float ws = ka->c[c].ws[0];
+#pragma unroll
+    for (int e = 0; e < 4; e++) p[c * 4 + e] = __fmul_rn(xq[c].v[e], ws);
+  }
+  constexpr int kN = L * 4;
+  float mx;
+  asm("v_maximum3_f32 %0, |%1|, |%2|, |%3|" : "=v"(mx) : "v"(p[0]), "v"(p[1]), "v"(p[2]));
+#pragma unroll
+  for (int i = 3; i < kN; i += 2)
+    asm("v_maximum3_f32 %0, %0, |%1|, |%2|" : "+v"(mx) : "v"(p[i]), "v"(p[i + 1 < kN ? i + 1 : i]));
+#pragma unroll
+  for (int c = 0; c < L; c++)
+#pragma unroll
+    for (int e = 0; e < 4; e++) q[c][e] = (int32_t)p[c * 4 + e];  // v_cvt_i32_f32 (saturating; NaN -> 0)
+  return !__any(!(mx < limit));
+}
+// ring word of two quantized values: sext64(q_even) + (sext64(q_odd) << 32)
+__device__ __forceinline__ uint64_t pack_word(int32_t q_even, int32_t q_odd) {
+  return (uint64_t)(int64_t)q_even + ((uint64_t)(uint32_t)q_odd << 32);
 }
 
 // ----------------------------------------------------------------------------
@@ -570,8 +657,10 @@ __device__ __forceinline__ void for_each_index(Fn&& f, std::integer_sequence<int
 // single-client kernel also carries the continue / per-element-weight /
 // DP-noise paths.  L = 8 (28 pair streams): 2 waves; 1 client + 7 cross
 // streams: 5.
-constexpr int clients_waves(int P, int L) {
-  const int regs = 4 * P + 4 * L * kE + 2 * L + (L == 1 ? 64 : 56);
+// A packed launch (kPacked) holds four inputs per client and lane instead of
+// two across the mask expansion: 2 more per client.
+constexpr int clients_waves(int P, int L, bool packed = false) {
+  const int regs = 4 * P + 4 * L * kE + 2 * L + (L == 1 ? 64 : 56) + (packed ? 2 * L : 0);
   const int w = 512 / regs;
   return w > 8 ? 8 : (w < 1 ? 1 : w);
 }
@@ -616,7 +705,7 @@ __device__ __forceinline__ kargs_t* fenced_args() {
 __device__ __forceinline__ void refence(kargs_t*& p) { asm volatile("" : "+s"(p)); }
 
 template <typename XT, typename CT, int L, int X, int K = kAllPairs>
-__global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::count + L * X, L))
+__global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::count + L * X, L, (K & kPacked) != 0))
     k_clients(const KArgs a) {
   constexpr int PI = Pairs<L, K>::count;
   constexpr int P = PI + L * X;
@@ -629,6 +718,11 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
   // cross streams only, masks only: one accumulator, nothing loaded
   constexpr bool kCross = (K & kCrossOnly) != 0;
   static_assert(!kCross || (L == 1 && !kGeneral), "kCrossOnly: one lean accumulator");
+  // two 32-bit values per ring word: n counts words, a.n_elems the inputs
+  constexpr bool kPack = (K & kPacked) != 0;
+  static_assert(!kPack || (std::is_same<XT, float>::value && std::is_same<CT, float>::value && !kGeneral &&
+                           !(K & (kBipartite | kCrossOnly))),
+                "kPacked: float32, no general paths, the clients' values enter here");
   static_assert(L >= 1 && L <= kMaxLocal, "L");
   static_assert(P <= kMaxStreams, "P");
 
@@ -698,6 +792,8 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
   // 0 iff some raw PCG64 draw of this lane (or, for the paired draws, of its
   // wave) was 0; the paired draws test per tile (sa_draw3.h, ZeroAcc)
   uint32_t zmin = 0xFFFFFFFFu;
+  // nonzero iff a tile of this wave failed the packed range vote
+  uint32_t range_bad = 0;
   SA_TS(ts1);
 
   // per-lane XOR digests of the clients' masked values: VGPRs, or for the
@@ -745,6 +841,7 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
     // ---- issue this tile's loads first; consumed after the mask expansion.
     // Unconditional: an absent vector has a 0-byte descriptor (reads 0).
     Vec2<XT> xv[L];
+    Vec4f xq[kPack ? L : 1];  // the packed tile's inputs (xv unused)
     Vec2<CT> wv[kGeneral ? L : 1];
     Vec2<uint64_t> pv[kGeneral ? L : 1];
     uint64_t acc[kE][L];  // per-client accumulators (negated<L> clients: -acc)
@@ -796,6 +893,8 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
           for (int k = 0; k < kE; k++) xv[c].v[k] = (XT)(int)(i + k + c);
         } else if constexpr (kMasksOnly) {
           xv[c].v[0] = xv[c].v[1] = (XT)0;
+        } else if constexpr (kPack) {
+          xq[c] = bload4_f32(make_rsrc(xp[c], ka->n_elems * sizeof(float)), i);
         } else {
           xv[c] = bload2<XT>(make_rsrc(xp[c], cont ? 0 : n * sizeof(XT)), i);
         }
@@ -971,6 +1070,43 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
         for (int c = L / 2 + 1; c < L; c++) B += acc[k][c];
         sum[k] = A - B;
       }
+    } else if constexpr (kPack) {
+      int32_t q[L][4];
+      if (__builtin_expect(!packed_quantize<L>(xq, ka, ka->pack_limit, q), 0)) range_bad = 1;
+      if (!dig_on && mmask == 0) {
+        // Only the sum leaves the tile: A - B as in the unpacked sum-only
+        // finish below; a client's word enters as q_even through the
+        // v_mad_i64_i32 and q_odd through one 32-bit add into the high dword
+#pragma unroll
+        for (int k = 0; k < kE; k++) {
+          uint64_t A = 0, B = 0;
+          bool a0 = false, b0 = false;
+#pragma unroll
+          for (int c = 0; c < L; c++) {
+            uint64_t& t = negated<L>(c) ? B : A;
+            bool& t0 = negated<L>(c) ? b0 : a0;
+            t = t0 ? t + acc[k][c] : acc[k][c];
+            t0 = true;
+          }
+#pragma unroll
+          for (int c = 0; c < L; c++) {
+            const int32_t qe = q[c][2 * k];
+            const uint64_t qo = (uint64_t)(uint32_t)q[c][2 * k + 1] << 32;
+            uint64_t kc;
+            if (negated<L>(c)) {
+              asm("v_mad_i64_i32 %[d], %[k], %[q], -1, %[d]" : [d] "+v"(B), [k] "=s"(kc) : [q] "v"(qe));
+              B -= qo;
+            } else {
+              asm("v_mad_i64_i32 %[d], %[k], %[q], 1, %[d]" : [d] "+v"(A), [k] "=s"(kc) : [q] "v"(qe));
+              A += qo;
+            }
+          }
+          sum[k] = A - B;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < L; c++) finish(c, pack_word(q[c][0], q[c][1]), pack_word(q[c][2], q[c][3]));
+      }
     } else if (cont) {  // a further pass: add the prior pass's masked vector
 #pragma unroll
       for (int c = 0; c < L; c++) finish(c, pv[kGeneral ? c : 0].v[0], pv[kGeneral ? c : 0].v[1]);
@@ -1053,6 +1189,9 @@ __global__ void __launch_bounds__(kBlockThreads, clients_waves(Pairs<L, K>::coun
   }
   if (a.flags && !(SA_ABLATE & 1) && __any(zmin == 0) && (threadIdx.x & 63) == 0)
     atomicOr(a.flags, SA_FLAG_PRG_REJECT);
+  if constexpr (kPack) {
+    if (a.flags && __any(range_bad != 0) && (threadIdx.x & 63) == 0) atomicOr(a.flags, SA_FLAG_PACK_RANGE);
+  }
 #ifdef SA_TIMING
   SA_TS(ts4);
   const uint32_t wid = blockIdx.x * (kBlockThreads / 64) + (threadIdx.x >> 6);
@@ -1079,15 +1218,20 @@ static_assert(kChunkElems % kTile == 0, "chunk");
 template <typename XT, typename CT, int L, int X, int K = kAllPairs>
 int launch_clients(const KArgs& in, void* stream) {
   constexpr int P = Pairs<L, K>::count + L * X;
+  constexpr int kPer = (K & kPacked) ? 2 : 1;  // input elements per ring word (in.n counts words)
   const void* kfn = reinterpret_cast<const void*>(&k_clients<XT, CT, L, X, K>);
   const int maxb = masking_grid_cap(kfn);
   if (maxb <= 0) return SA_ERR_HIP;
   for (uint64_t off = 0; off < in.n; off += kChunkElems) {
     KArgs a = in;
     a.n = in.n - off < kChunkElems ? in.n - off : kChunkElems;
+    if (kPer == 2) {  // this chunk's input elements: two per word, less the odd tail's missing one
+      const uint64_t left = in.n_elems - off * 2;
+      a.n_elems = left < a.n * 2 ? left : a.n * 2;
+    }
     if (off) {
       for (int c = 0; c < L; c++) {
-        if (a.c[c].x) a.c[c].x = static_cast<const XT*>(a.c[c].x) + off;
+        if (a.c[c].x) a.c[c].x = static_cast<const XT*>(a.c[c].x) + off * kPer;
         if (a.c[c].wvec) a.c[c].wvec = static_cast<const CT*>(a.c[c].wvec) + off;
         if (a.c[c].masked_out) a.c[c].masked_out += off;
       }

@@ -86,6 +86,12 @@ constexpr int kSumOnly = 4;
 // multi-launch schedule, e.g. 4 local clients + 28 cross streams each at 32
 // clients over 8 GPUs).  Used as kLean1 | kSumOnly | kCrossOnly.
 constexpr int kCrossOnly = 8;
+// kPacked: two 32-bit fixed-point values per ring word (pack=2, float32
+// only): the lane's two words hold four input elements, KArgs::n counts
+// words, KArgs::n_elems the input elements (sa_clients_impl.h, "The packed
+// variant").  Used as kPacked [| kSumOnly] for 2..8 co-located clients and
+// kPacked | kLean1 for one; instantiated in sa_clients_pack2.hip.
+constexpr int kPacked = 16;
 // the stream counts instantiated for kCrossOnly (sa_clients_f32.hip), largest
 // first: a schedule takes the largest that fits its remaining streams, so any
 // count is covered (the per-rank shapes of the benches by the first three)
@@ -172,6 +178,11 @@ struct KArgs {
   const double* dp_sumsq;
   const double* dp_sumsq_layer;
   uint64_t dp_key, dp_block0;  // Philox key; counter block of element 0
+  // kPacked launches only: the input vectors' element count (n counts ring
+  // words, ceil(n_elems / 2)) and the range rule's bound on |x * w * 2^fxp|,
+  // the largest float32 not above 2^31 / parties
+  uint64_t n_elems;
+  float pack_limit;
 };
 
 static_assert(sizeof(KArgs) <= 4096, "kernel arguments must fit the 4 KiB kernarg segment");
@@ -182,5 +193,8 @@ typedef int (*LaunchFn)(const KArgs& a, void* stream);
 // K: pair set of the launch (0: every internal pair of the L clients; 1:
 // bipartite, the pairs between the lower and upper half -- sa_fused_bipartite)
 LaunchFn find_clients_kernel(int xt, int ct, int L, int X, int K = kAllPairs);
+// The packed (kPacked) float32 instantiations, sa_clients_pack2.hip: K with
+// or without the kPacked bit; nullptr when not instantiated.
+LaunchFn find_pack2_kernel(int L, int X, int K);
 
 }  // namespace sa

@@ -130,6 +130,53 @@ __global__ void __launch_bounds__(256) k_decode_unaligned(const uint64_t* __rest
     out[i] = decode1(s[i], inv_scale, divv ? divv[i] : div);
 }
 
+// Packed decode (pack=2): a summed ring word S holds two 32-bit sums,
+// lo = (int32)S and hi = (int32)((S >> 32) + (lo < 0)) -- the sign extension
+// of the clients' low halves borrowed one from the high half per negative low
+// value, i.e. 1 iff the low SUM is negative (the range rule keeps both sums in
+// 32 bits).  The int32 -> double conversions, the scaling and the division
+// are decode1's, so the values equal the unpacked decode's bit for bit.
+__device__ __forceinline__ f64x2 decode_word(uint64_t S, double inv_scale, double div) {
+  const int32_t lo = (int32_t)(uint32_t)S;
+  const int32_t hi = (int32_t)((uint32_t)(S >> 32) + (lo < 0 ? 1u : 0u));
+  return f64x2{decode1((uint64_t)(int64_t)lo, inv_scale, div), decode1((uint64_t)(int64_t)hi, inv_scale, div)};
+}
+
+// out 16-B aligned: a lane reads one word (8-B load, 512 B contiguous a wave
+// instruction) and writes its two doubles in one 16-B store (1 KiB
+// contiguous), over k_decode's tile (kTileAccesses words a block).  The form
+// first built -- two words in one 16-B load, four doubles in two 16-B stores
+// 32 B apart between lanes -- ran at 0.35 of the HBM peak, below the unpacked
+// decode: each store instruction filled only half of every
+// line it touched.  n elements in ceil(n / 2)
+// words; an odd n's half-filled last word is done by one lane of block 0.
+__global__ void __launch_bounds__(256) k_decode_pack2(const uint64_t* __restrict__ s, uint64_t n, double inv_scale,
+                                                      double div, double* __restrict__ out) {
+  const uint64_t full = n / 2;  // words whose two elements both exist
+  const uint64_t base = (uint64_t)blockIdx.x * kTileAccesses + threadIdx.x;
+  f64x2* o2 = reinterpret_cast<f64x2*>(out);
+  uint64_t v[kUnroll];
+#pragma unroll
+  for (int u = 0; u < kUnroll; u++) v[u] = base + u * 256 < full ? ld_nt(s + base + u * 256) : 0;
+#pragma unroll
+  for (int u = 0; u < kUnroll; u++)
+    if (base + u * 256 < full) st_nt(o2 + base + u * 256, decode_word(v[u], inv_scale, div));
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = decode_word(s[full], inv_scale, div).x;
+}
+
+// any alignment: one word per lane
+__global__ void __launch_bounds__(256) k_decode_pack2_unaligned(const uint64_t* __restrict__ s, uint64_t n,
+                                                                double inv_scale, double div,
+                                                                double* __restrict__ out) {
+  const uint64_t nw = (n + 1) / 2;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nw; j += stride) {
+    const f64x2 d = decode_word(s[j], inv_scale, div);
+    out[2 * j] = d.x;
+    if (2 * j + 1 < n) out[2 * j + 1] = d.y;
+  }
+}
+
 // one block per tile of kTileAccesses 16-B accesses (at least one block for
 // the odd-element lane)
 static int tile_grid(uint64_t n) {
@@ -214,6 +261,19 @@ extern "C" int sa_decode(const uint64_t* s, uint64_t n, int fxp_bits, double div
   const bool vec = aligned16(s) && aligned16(out) && aligned16(divisor_vec);
   const auto fn = !vec ? &k_decode_unaligned : divisor_vec ? &k_decode<true> : &k_decode<false>;
   return launch_server(fn, vec, n, stream, s, n, inv_scale, divisor, divisor_vec, out);
+}
+
+extern "C" int sa_decode_pack2(const uint64_t* s_words, uint64_t n, int fxp_bits, double divisor, double* out,
+                               void* stream) {
+  if (fxp_bits < 0 || fxp_bits > 30 || (n > 0 && (!s_words || !out))) {
+    sa_set_error("sa_decode_pack2: bad arguments (fxp_bits=%d, want 0..30)", fxp_bits);
+    return SA_ERR_ARG;
+  }
+  if (n == 0) return SA_OK;
+  const double inv_scale = 1.0 / (double)((uint64_t)1 << fxp_bits);
+  // the tiled kernel's grid: one access a full word (tile_grid halves its count)
+  if (aligned16(out)) return launch_server(&k_decode_pack2, true, n, stream, s_words, n, inv_scale, divisor, out);
+  return launch_server(&k_decode_pack2_unaligned, false, (n + 1) / 2, stream, s_words, n, inv_scale, divisor, out);
 }
 
 extern "C" int sa_sum_f64(const double* const* w, int k, uint64_t n, double* out, void* stream) {

@@ -247,6 +247,70 @@ def decode(s: torch.Tensor, out: torch.Tensor, *, fxp_bits: int = 18, divisor: f
     return out
 
 
+# ---------------------------------------------------------------------------
+# pack=2: two 32-bit fixed-point values per ring word (sa_*_pack2)
+# ---------------------------------------------------------------------------
+def _pack2_operands(who: str, x: torch.Tensor, words: torch.Tensor) -> int:
+    if x.dtype != torch.float32 or words.numel() != (x.numel() + 1) // 2:
+        raise ValueError(f"{who}: float32 x and ceil(n / 2) ring words")
+    return x.numel()
+
+
+def mask_pack2(x: torch.Tensor, out_words: torch.Tensor, streams: Sequence[tuple], n_clients: int, *,
+               weight: float = 1.0, fxp_bits: int = 18, sum_accum: torch.Tensor | None = None,
+               digest: torch.Tensor | None = None, flags: torch.Tensor | None = None) -> torch.Tensor:
+    """One client's masked PACKED vector: ``out_words`` (ceil(n / 2) words) =
+    pack_words(trunc(x*w*2^fxp)) +/- masks (mod 2^64); ``n_clients``: the
+    parties of the aggregation (the range rule).  See sa_mask_pack2 in
+    include/sfl_sa.h."""
+    _require_gpu(x, out_words, sum_accum, digest, flags)
+    n = _pack2_operands("mask_pack2", x, out_words)
+    sarr = make_streams(streams)
+    L.check(L.lib().sa_mask_pack2(_ptr(x), n, float(weight), int(fxp_bits), int(n_clients), sarr, len(streams),
+                                  _ptr(out_words), _ptr(sum_accum), _ptr(digest), _ptr(flags),
+                                  C.c_void_p(_stream(out_words))), "sa_mask_pack2")
+    return out_words
+
+
+def fused_clients_pack2(xs: Sequence[torch.Tensor], weights: Sequence[float], pair_gens: Sequence,
+                        pair_signs: Sequence[int], sum_out_words: torch.Tensor, *, fxp_bits: int = 18,
+                        accumulate: bool = False, digests: torch.Tensor | None = None,
+                        flags: torch.Tensor | None = None,
+                        masked_outs: Sequence[torch.Tensor | None] | None = None) -> torch.Tensor:
+    """2..8 co-located clients (all the parties) in one PACKED launch: the
+    masked sum of their ceil(n / 2) ring words.  See sa_fused_clients_pack2
+    in include/sfl_sa.h."""
+    _require_gpu(sum_out_words, digests, flags, *xs)
+    nc = len(xs)
+    n = _pack2_operands("fused_clients_pack2", xs[0], sum_out_words)
+    clients = (L.LocalClient * nc)()
+    for c, x in enumerate(xs):
+        if x.numel() != n or x.dtype != torch.float32:
+            raise ValueError("fused clients need equal-size float32 vectors")
+        mo = masked_outs[c] if masked_outs else None
+        if mo is not None and mo.numel() != sum_out_words.numel():
+            raise ValueError("a packed wire image has ceil(n / 2) words")
+        clients[c].x, clients[c].weight = x.data_ptr(), float(weights[c])
+        clients[c].masked_out = mo.data_ptr() if mo is not None else None
+    pg, ps = _pair_arrays(nc, pair_gens, pair_signs)
+    L.check(L.lib().sa_fused_clients_pack2(clients, nc, n, int(fxp_bits), pg, ps, _ptr(sum_out_words),
+                                           int(bool(accumulate)), _ptr(digests), _ptr(flags),
+                                           C.c_void_p(_stream(sum_out_words))), "sa_fused_clients_pack2")
+    return sum_out_words
+
+
+def decode_pack2(s_words: torch.Tensor, out: torch.Tensor, *, fxp_bits: int = 18,
+                 divisor: float = 1.0) -> torch.Tensor:
+    """float64 out (n) from the summed packed words (ceil(n / 2)): both
+    32-bit halves, the borrow undone, / 2^fxp / divisor.  See sa_decode_pack2."""
+    _require_gpu(s_words, out)
+    if s_words.numel() != (out.numel() + 1) // 2:
+        raise ValueError("decode_pack2: ceil(n / 2) ring words for n outputs")
+    L.check(L.lib().sa_decode_pack2(_ptr(s_words), out.numel(), int(fxp_bits), float(divisor), _ptr(out),
+                                    C.c_void_p(_stream(out))), "sa_decode_pack2")
+    return out
+
+
 def _scratch(pinned: torch.Tensor, dev: torch.Tensor, need_pin: int, need_dev: int) -> None:
     _require_gpu(dev)
     if not pinned.is_pinned() or pinned.numel() < need_pin or dev.numel() < need_dev:

@@ -31,6 +31,11 @@ take go through the general path above.
 
 Which of these a call takes is decided in one place, ``SecureAggregator._route``
 (the route table: DESIGN.md §7); each route is one ``_run_<route>`` method.
+
+``pack=2`` is a route of its own, ``_run_pack2``: float32
+payloads with scalar weights, two 32-bit fixed-point values per ring word --
+half the draws, sum bytes and wire bytes, bit-identical results while every
+``|x * w| < 2^(31 - fxp_bits) / C``, an ``OverflowError`` otherwise.
 """
 
 from __future__ import annotations
@@ -53,6 +58,7 @@ from .payload import (F32, F64, I64, SMALL_CALL_BYTES, compute_dtype, element_ty
 
 MAX_FUSED_CLIENTS = 8  # parties of one fused launch (sa_fused_clients, sa_fused_clients_host_f32)
 MAX_HOST_CLIENTS = 9   # parties of one sa_clients_host call
+MAX_PACK2_CLIENTS = 17  # pack=2 parties: one sa_mask_pack2 pass holds a party's 16 pair streams
 
 
 class _Rejected(Exception):
@@ -135,6 +141,15 @@ class SecureAggregator(Aggregator):
         keep_masked: also materialise every party's masked vector (the wire
             image) and expose the last ones as ``last_masked``; co-located
             parties still take the fused launch, which stores the images.
+        pack: 1 (default) one fixed-point value per 64-bit ring word; 2 two
+            32-bit values per word (float32 payloads, scalar or no weights,
+            at most 17 parties): masked per layer, each layer starting on a
+            word boundary and advancing the streams by ``ceil(n / 2)``;
+            ``last_masked`` / ``last_digests`` then hold, per layer, the
+            parties' word images and their digests.  Results equal
+            ``pack=1``'s bit for bit; a value outside the range rule raises
+            ``OverflowError``, anything else unsupported
+            ``NotImplementedError``.
 
     ``last_digests``: per launch group of the last aggregation, the XOR
     digest of every party's masked vector (a checksum the tests pin) -- None
@@ -143,8 +158,13 @@ class SecureAggregator(Aggregator):
     """
 
     def __init__(self, device: PYU, participants: List[PYU], fxp_bits: int = 18, *,
-                 seeds: dict | None = None, fused: bool = True, keep_masked: bool = False):
+                 seeds: dict | None = None, fused: bool = True, keep_masked: bool = False, pack: int = 1):
         assert participants, "participants should not be empty"
+        if pack not in (1, 2):
+            raise ValueError(f"pack must be 1 or 2, not {pack!r}")
+        if pack == 2 and not 0 <= int(fxp_bits) <= 30:
+            raise ValueError(f"pack=2 takes fxp_bits 0..30, not {fxp_bits}")
+        self._pack = pack
         names = [p.party for p in participants]
         assert len(set(names)) == len(names), f"duplicate participants: {names}"
         self._device = device
@@ -221,7 +241,8 @@ class SecureAggregator(Aggregator):
 
     def _aggregate_once(self, data, axis, weights, average: bool) -> DeviceObject:
         call = self._build_call(data, self._validate(data, axis, weights), average)
-        return getattr(self, "_run_" + self._route(call))(call)
+        route = "pack2" if self._pack == 2 else self._route(call)
+        return getattr(self, "_run_" + route)(call)
 
     def _validate(self, data, axis, weights):
         """The reference's argument checks; returns the weights on the host."""
@@ -303,6 +324,88 @@ class SecureAggregator(Aggregator):
         if not call.as_torch and len(call.sizes) > 1 and call.scalar_w and call.one_dtype_each:
             return "general_host_packed"
         return "general"
+
+    # ------------------------------------- route: pack=2 (two values per ring word)
+    def _run_pack2(self, call: _Call):
+        """Every layer packed on its own (``n_l`` elements in ``ceil(n_l /
+        2)`` words, the streams advancing by that many draws): 2..8
+        co-located parties by the fused packed launch, otherwise each party's
+        ``sa_mask_pack2`` on its own GPU, the word images moved to the server
+        and summed there; then the packed decode.  CUDA tensors are masked in
+        place, host arrays copied in and the result copied out through
+        ``hostpipe``.  The replay after a flagged raw 0 is ``_fix_rejections``
+        on words (the word images are materialised for it)."""
+        C, fxp = call.C, self._fxp_bits
+        if call.ldts != {F32} or call.cts != {F32} or not call.scalar_w:
+            raise NotImplementedError("pack=2 takes float32 payloads with scalar weights that keep float32 "
+                                      f"arithmetic (layer dtypes {sorted(map(str, call.ldts))}, arithmetic "
+                                      f"{sorted(map(str, call.cts))}, scalar weights: {call.scalar_w})")
+        if C > MAX_PACK2_CLIENTS:
+            raise NotImplementedError(f"pack=2 takes at most {MAX_PACK2_CLIENTS} parties, not {C}")
+        sdev = self._device.torch_device
+        parties = [d.device for d in call.data]
+        names, ws = call.names, call.scalar_weights()
+        fusable = self._fused and 2 <= C <= MAX_FUSED_CLIENTS and call.colocated
+        keep = self._keep_masked or self._careful
+        flags = torch.zeros(1, dtype=torch.int32, device=sdev)
+        out_layers, masked_keep, digests_keep = [], [], []
+        for li, n in enumerate(call.sizes):
+            nw = (n + 1) // 2
+            xs = [to_device(ll[li], F32, p.torch_device) for ll, p in zip(call.layer_lists, parties)]
+            s = torch.empty(nw, dtype=K.U64, device=sdev)
+            digests = torch.zeros(C, dtype=K.U64, device=sdev)
+            pair_gens, pair_signs = self._pair_streams(names, fusable or self._careful)
+            streams = None if fusable and not self._careful else [self._maskers[nm].streams() for nm in names]
+            if fusable:
+                masked = [torch.empty(nw, dtype=K.U64, device=sdev) for _ in range(C)] if keep else None
+                with torch.cuda.device(sdev):
+                    K.fused_clients_pack2(xs, ws, pair_gens, pair_signs, s, fxp_bits=fxp, digests=digests,
+                                          flags=flags, masked_outs=masked)
+            else:
+                masked = []
+                for ci, p in enumerate(parties):
+                    pdev = p.torch_device
+                    local = pdev == sdev
+                    out = torch.empty(nw, dtype=K.U64, device=pdev)
+                    dig = digests[ci:ci + 1] if local else torch.zeros(1, dtype=K.U64, device=pdev)
+                    fl = flags if local else torch.zeros(1, dtype=torch.int32, device=pdev)
+                    with torch.cuda.device(pdev):
+                        K.mask_pack2(xs[ci], out, streams[ci], C, weight=ws[ci], fxp_bits=fxp, digest=dig, flags=fl)
+                    if not local:
+                        flags |= fl.to(sdev)
+                        digests[ci] = dig.to(sdev)[0]
+                    masked.append(out if local else out.to(sdev))  # the wire: half the words of pack=1
+                with torch.cuda.device(sdev):
+                    K.sum_u64(masked, s)
+            extra = {}
+            if self._careful:
+                torch.cuda.synchronize(sdev)
+                if int(flags.item()) & L.SA_FLAG_PRG_REJECT:
+                    g = _Group(nw, xs, [F32] * C, ws, [None] * C)
+                    extra = self._fix_rejections(names, pair_gens, pair_signs, streams, g, masked, digests, s)
+                    flags &= ~L.SA_FLAG_PRG_REJECT
+            for nm in names:
+                self._maskers[nm].consume(nw)
+            for (a, b), k in extra.items():
+                self._maskers[a].skip(b, k)
+                self._maskers[b].skip(a, k)
+            dec = torch.empty(n, dtype=torch.float64, device=sdev)
+            with torch.cuda.device(sdev):
+                K.decode_pack2(s, dec, fxp_bits=fxp, divisor=call.divisor())
+            out_layers.append(dec)
+            masked_keep.append(masked)
+            digests_keep.append(digests)
+        flag = int(flags.item())
+        if flag & L.SA_FLAG_PACK_RANGE:
+            raise OverflowError(f"pack=2: a value is NaN or outside the range rule: with fxp_bits={fxp} and C={C} "
+                                f"parties every |x * w| must stay below 2^(31 - {fxp}) / {C} = "
+                                f"{2.0 ** (31 - fxp) / C:g}; use pack=1 for such payloads")
+        if flag & L.SA_FLAG_PRG_REJECT:
+            raise _Rejected()
+        if self._keep_masked:
+            self.last_masked = masked_keep
+        self.last_digests = digests_keep
+        return call.pack([(d if call.as_torch else H.d2h(d)).reshape(sh) for d, sh in zip(out_layers, call.shapes)])
 
     # --------------------------------------------- routes: float32, fused launch
     def _staging(self, C: int, n_pad: int, sdev):
