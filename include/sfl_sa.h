@@ -1022,6 +1022,49 @@ int sa_fused_clients_pack2(const sa_local_client* clients, int n_clients, uint64
 int sa_decode_pack2(const uint64_t* s_words, uint64_t n, int fxp_bits, double divisor, double* out,
                     void* stream);
 
+/* ------------------------------------------------------------------ */
+/* MarsAggregator: the features of the reference's Lipschitz-based      */
+/* robust aggregator (examples/security/h_bd/agg_mars.py:27-153, CLP)   */
+/* for C clients, 0 <= C <= SA_FLAME_MAX_CLIENTS, whose layers of       */
+/* x_type T (SA_F32 or SA_F64) live on one device.  w, bn_w and bn_var  */
+/* are HOST tables of C device pointers; they reach the kernels by      */
+/* value.  sfl_amd/security/aggregation/mars_aggregator.py has the      */
+/* definition, the host form and the decisions.  All features float64:  */
+/*   scale[ch] = |float64(bn_w[ch])| / sqrt(max(float64(bn_var[ch]), 0) */
+/*           + 1e-5)  (agg_mars.py:94-95 and :119-121)                  */
+/*   sa_mars_sigma   one layer of all clients: w[c] points to n_mat     */
+/*           matrices of rows x cols, row-major and contiguous (a conv  */
+/*           layer: n_mat = C_out, rows = C_in, cols = kh kw, agg_mars. */
+/*           py:89-106; an fc layer: n_mat = 1, :129-135).              */
+/*           out[c n_mat + m] = sigma(matrix m of client c), its        */
+/*           largest singular value from the float64 Gram matrix (the   */
+/*           operands converted first, so float32 products are exact)   */
+/*           of the smaller side p = min(rows, cols) by cyclic Jacobi;  */
+/*           times scale[m] of the client's bn_w / bn_var for m < n_bn  */
+/*           (n_bn == 0: the tables are not looked at).  One wave per   */
+/*           (client, matrix); the same input gives the same bits.  An  */
+/*           all-zero matrix gives 0.0; a NaN or an infinity in a       */
+/*           matrix gives that matrix a non-finite value and costs no   */
+/*           sweep.  p must be in 1..SA_MARS_MAX_P: a larger one is     */
+/*           refused with SA_ERR_UNSUPPORTED and nothing is computed    */
+/*           (the class takes such layers on the host).                 */
+/*   sa_mars_bn      out[c n_bn + ch] = scale[ch] of client c.          */
+/* n_clients == 0, n_mat == 0 and n_bn == 0 (sa_mars_bn) return SA_OK   */
+/* after the checks of the scalars and look at no pointer.  Other       */
+/* element types, a client count outside 0..SA_FLAME_MAX_CLIENTS,       */
+/* n_mat, rows or cols >= 2^24, n_bn >= 2^32 (sa_mars_bn), null and     */
+/* misaligned pointers are refused before any launch.  Everything is    */
+/* stream-ordered, allocates nothing, uses no atomics and never         */
+/* synchronises with the host.  ABI version 3 (additive).               */
+/* ------------------------------------------------------------------ */
+#define SA_MARS_MAX_P 32
+
+int sa_mars_sigma(const void* const* w, int n_clients, int x_type, uint64_t n_mat, uint64_t rows, uint64_t cols,
+                  const void* const* bn_w, const void* const* bn_var, uint64_t n_bn, double* out, void* stream);
+
+int sa_mars_bn(const void* const* bn_w, const void* const* bn_var, int n_clients, int x_type, uint64_t n_bn,
+               double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

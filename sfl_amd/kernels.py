@@ -1204,3 +1204,78 @@ def flame_combine(xs: Sequence, scales: Sequence[float], weights: Sequence[float
     L.check(L.lib().sa_flame_combine(table, s, w, c, _XTYPE.get(median.dtype, -1), n, _ptr(median), float(divisor),
                                      _ptr(out), C.c_void_p(_stream(median))), "sa_flame_combine")
     return out
+
+
+# ---------------------------------------------------------------------------
+# MarsAggregator (sa_mars_*; security/aggregation/mars_aggregator.py on top)
+# ---------------------------------------------------------------------------
+def _mars_table(what: str, name: str, xs: Sequence, numel: int, like: torch.Tensor) -> C.Array:
+    """The host table of one argument's device pointers, one client each: a
+    contiguous tensor of ``numel`` elements of ``like``'s dtype on its device,
+    or -- handed to the library as it is, which refuses what it cannot take --
+    ``None`` or an address."""
+    table = (C.c_void_p * max(1, len(xs)))()
+    for i, x in enumerate(xs):
+        if isinstance(x, torch.Tensor):
+            _require_gpu(x)
+            if x.dtype != like.dtype or x.numel() != numel or not x.is_contiguous() or x.device != like.device:
+                raise ValueError(f"{what}: client {i}'s {name} is contiguous, {numel} elements of one dtype on one device")
+            table[i] = x.data_ptr()
+        else:
+            table[i] = x
+    return table
+
+
+def _mars_out(what: str, out: torch.Tensor, offset: int, count: int) -> C.c_void_p:
+    _require_gpu(out)
+    if out.dtype != torch.float64 or not out.is_contiguous() or offset < 0 or offset + count > out.numel():
+        raise ValueError(f"{what}: out is contiguous float64 with room for {count} values at offset {offset}")
+    return C.c_void_p(out.data_ptr() + 8 * offset)
+
+
+def _mars_like(what: str, xs: Sequence) -> torch.Tensor:
+    like = next((x for x in xs if isinstance(x, torch.Tensor)), None)
+    if like is None:
+        raise ValueError(f"{what}: at least one client's tensor")
+    _require_gpu(like)
+    return like
+
+
+def mars_sigma(ws: Sequence, n_mat: int, rows: int, cols: int, out: torch.Tensor, offset: int = 0, *,
+               bn_w: Sequence = (), bn_var: Sequence = ()) -> torch.Tensor:
+    """``out[offset + c * n_mat + m]`` (float64) = the largest singular value
+    of matrix ``m`` (``rows x cols``, row-major) of client ``c``'s tensor
+    ``ws[c]``; with ``bn_w`` / ``bn_var`` (one tensor per client, ``n_bn``
+    channels) times ``|bn_w[m]| / sqrt(max(bn_var[m], 0) + 1e-5)`` for
+    ``m < n_bn``.  ``min(rows, cols)`` above ``SA_MARS_MAX_P`` is refused by
+    the library.  See sa_mars_sigma in include/sfl_sa.h."""
+    c = len(ws)
+    like = _mars_like("mars_sigma", ws)
+    if len(bn_w) != len(bn_var) or len(bn_w) not in (0, c):
+        raise ValueError("mars_sigma: bn_w and bn_var are one tensor per client each, or both empty")
+    n_bn = 0
+    if len(bn_w):
+        first = _mars_like("mars_sigma", bn_w)
+        n_bn = first.numel()
+    table = _mars_table("mars_sigma", "tensor", ws, n_mat * rows * cols, like)
+    tw = _mars_table("mars_sigma", "bn_w", bn_w, n_bn, like) if n_bn else None
+    tv = _mars_table("mars_sigma", "bn_var", bn_var, n_bn, like) if n_bn else None
+    L.check(L.lib().sa_mars_sigma(table, c, _XTYPE.get(like.dtype, -1), int(n_mat), int(rows), int(cols), tw, tv, n_bn,
+                                  _mars_out("mars_sigma", out, offset, c * n_mat), C.c_void_p(_stream(like))),
+            "sa_mars_sigma")
+    return out
+
+
+def mars_bn(bn_w: Sequence, bn_var: Sequence, out: torch.Tensor, offset: int = 0) -> torch.Tensor:
+    """``out[offset + c * n_bn + ch]`` (float64) = ``|bn_w[ch]| /
+    sqrt(max(bn_var[ch], 0) + 1e-5)`` of client ``c``.  See sa_mars_bn."""
+    c = len(bn_w)
+    like = _mars_like("mars_bn", bn_w)
+    if len(bn_var) != c:
+        raise ValueError("mars_bn: one bn_w and one bn_var per client")
+    n_bn = like.numel()
+    tw = _mars_table("mars_bn", "bn_w", bn_w, n_bn, like)
+    tv = _mars_table("mars_bn", "bn_var", bn_var, n_bn, like)
+    L.check(L.lib().sa_mars_bn(tw, tv, c, _XTYPE.get(like.dtype, -1), n_bn, _mars_out("mars_bn", out, offset, c * n_bn),
+                               C.c_void_p(_stream(like))), "sa_mars_bn")
+    return out
