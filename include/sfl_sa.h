@@ -1065,6 +1065,50 @@ int sa_mars_sigma(const void* const* w, int n_clients, int x_type, uint64_t n_ma
 int sa_mars_bn(const void* const* bn_w, const void* const* bn_var, int n_clients, int x_type, uint64_t n_bn,
                double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* FreqAggregator: the features of the reference's FreqFed robust       */
+/* aggregator (examples/security/h_bd/agg_freqfed.py) for C clients,    */
+/* 0 <= C <= SA_FLAME_MAX_CLIENTS, whose rows x cols layer of x_type T  */
+/* (SA_F32 or SA_F64) lives on one device.  w is a HOST table of C      */
+/* device pointers; it reaches the kernels by value.  sfl_amd/security/ */
+/* aggregation/freq_aggregator.py has the definition, the host form     */
+/* and the decisions.  With h = rows / 2, w = cols / 2, q = (rows +     */
+/* cols) / 4 (integer divisions), hk = min(h, q + 1), wk = min(w,       */
+/* q + 1):                                                              */
+/*   sa_freq_features  feats_out[c hk wk + i wk + j] = V_c[i][j] for    */
+/*           i + j <= q, else +0.0, where V_c = C_rows W_c C_cols^T is  */
+/*           the orthonormal 2-D DCT-II of client c's matrix in float64 */
+/*           (the operands converted first), C_n[k][i] = s_k cos(pi (2  */
+/*           i + 1) k / (2 n)), s_0 = sqrt(1 / n), s_k = sqrt(2 / n):   */
+/*           what tensorDCT's dct calls per row and per column and      */
+/*           filtering's double loop compute (agg_freqfed.py:26-61), as */
+/*           two float64 matrix products on v_mfma_f64_16x16x4_f64 with */
+/*           a basis whose angles are reduced exactly in integers.  The */
+/*           order of every sum is a function of the shapes: the same   */
+/*           input gives the same bits.  scratch: sa_freq_scratch_bytes */
+/*           bytes, 8-byte aligned (the basis and every client's first  */
+/*           product); a size above 2^31 - 1 is refused with            */
+/*           SA_ERR_UNSUPPORTED and nothing is computed (the class      */
+/*           takes such layers on the host).                            */
+/*   sa_freq_gram      out[s] = sum_e feats[i len + e] feats[j len + e] */
+/*           in float64 for the pairs i <= j < C, s counting them row   */
+/*           by row (the upper triangle, C (C + 1) / 2 values): the dot */
+/*           products of the cosine distances (agg_freqfed.py:80-87),   */
+/*           each a fixed-order sum of one block.                       */
+/* n_clients == 0 returns SA_OK after the checks of the scalars and     */
+/* looks at no pointer.  Other element types, a client count outside    */
+/* 0..SA_FLAME_MAX_CLIENTS, rows or cols below 2 or >= 2^24, len >=     */
+/* 2^32, null and misaligned pointers are refused before any launch.    */
+/* Everything is stream-ordered, allocates nothing, uses no atomics and */
+/* never synchronises with the host.  ABI version 3 (additive).         */
+/* ------------------------------------------------------------------ */
+int sa_freq_scratch_bytes(uint64_t rows, uint64_t cols, int n_clients, int x_type);
+
+int sa_freq_features(const void* const* w, int n_clients, int x_type, uint64_t rows, uint64_t cols, void* scratch,
+                     double* feats_out, void* stream);
+
+int sa_freq_gram(const double* feats, int n_clients, uint64_t len, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ EXPORTED = (
     "sa_kmeans_scratch_bytes", "sa_kmeans_hist", "sa_kmeans_step", "sa_kmeans_labels", "sa_dequant_lut",
     "sa_flame_scratch_bytes", "sa_flame_stats", "sa_flame_combine",
     "sa_mars_sigma", "sa_mars_bn",
+    "sa_freq_scratch_bytes", "sa_freq_features", "sa_freq_gram",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
     "sa_smp_mask_host", "sa_smp_mask", "sa_smp_delta_f32", "sa_smp_sumsq_f32", "sa_smp_perturb_f32",
     "sa_smp_finish_f32",
@@ -188,6 +189,9 @@ def _declare(lib):
     lib.sa_flame_combine.argtypes = [P(C.c_void_p), P(C.c_double), P(C.c_double), i32, i32, u64, vp, dbl, vp, vp]
     lib.sa_mars_sigma.argtypes = [P(C.c_void_p), i32, i32, u64, u64, u64, P(C.c_void_p), P(C.c_void_p), u64, vp, vp]
     lib.sa_mars_bn.argtypes = [P(C.c_void_p), P(C.c_void_p), i32, i32, u64, vp, vp]
+    lib.sa_freq_scratch_bytes.argtypes = [u64, u64, i32, i32]
+    lib.sa_freq_features.argtypes = [P(C.c_void_p), i32, i32, u64, u64, vp, vp, vp]
+    lib.sa_freq_gram.argtypes = [vp, i32, u64, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -1279,3 +1279,52 @@ def mars_bn(bn_w: Sequence, bn_var: Sequence, out: torch.Tensor, offset: int = 0
     L.check(L.lib().sa_mars_bn(tw, tv, c, _XTYPE.get(like.dtype, -1), n_bn, _mars_out("mars_bn", out, offset, c * n_bn),
                                C.c_void_p(_stream(like))), "sa_mars_bn")
     return out
+
+
+# ---------------------------------------------------------------------------
+# FreqAggregator (sa_freq_*; security/aggregation/freq_aggregator.py on top)
+# ---------------------------------------------------------------------------
+def freq_corner(rows: int, cols: int) -> tuple:
+    """``(hk, wk, q)`` of a ``rows x cols`` layer: the feature is the ``hk x wk``
+    corner of its DCT, zero where ``i + j > q``."""
+    q = (rows + cols) // 4
+    return min(rows // 2, q + 1), min(cols // 2, q + 1), q
+
+
+def freq_scratch_bytes(rows: int, cols: int, n_clients: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``freq_features`` needs; a size the library does
+    not take raises ``SALibraryError`` with code ``SA_ERR_UNSUPPORTED``."""
+    return _scratch_bytes("freq_scratch_bytes", "sa_freq_scratch_bytes", (rows, cols, n_clients), dtype)
+
+
+def freq_features(ws: Sequence, rows: int, cols: int, scratch: torch.Tensor, feats_out: torch.Tensor) -> torch.Tensor:
+    """``feats_out[c]`` (float64, ``hk * wk`` values a client) = the filtered
+    low-frequency corner of the 2-D DCT of client ``c``'s ``rows x cols``
+    tensor ``ws[c]``.  See sa_freq_features in include/sfl_sa.h."""
+    c = len(ws)
+    like = _mars_like("freq_features", ws)
+    _require_gpu(scratch, feats_out)
+    hk, wk, _ = freq_corner(rows, cols)
+    if feats_out.dtype != torch.float64 or not feats_out.is_contiguous() or feats_out.numel() < c * hk * wk:
+        raise ValueError(f"freq_features: feats_out is contiguous float64 with room for {c} x {hk * wk} values")
+    xt = _XTYPE.get(like.dtype, -1)
+    if 1 <= c <= L.SA_FLAME_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64) and rows >= 2 and cols >= 2:
+        _require_scratch("freq_features", scratch, freq_scratch_bytes(rows, cols, c, like.dtype),
+                         "freq_scratch_bytes(rows, cols, n_clients, dtype)")
+    table = _mars_table("freq_features", "tensor", ws, rows * cols, like)
+    L.check(L.lib().sa_freq_features(table, c, xt, int(rows), int(cols), _ptr(scratch), _ptr(feats_out),
+                                     C.c_void_p(_stream(like))), "sa_freq_features")
+    return feats_out
+
+
+def freq_gram(feats: torch.Tensor, n_clients: int, length: int, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float64) = the packed upper triangle of the Gram matrix of the
+    ``n_clients`` rows of ``length`` float64 values in ``feats``.  See sa_freq_gram."""
+    _require_gpu(feats, out)
+    if feats.dtype != torch.float64 or out.dtype != torch.float64 or not feats.is_contiguous() \
+            or not out.is_contiguous() or feats.numel() < n_clients * length \
+            or out.numel() < n_clients * (n_clients + 1) // 2:
+        raise ValueError("freq_gram: contiguous float64 tensors, n_clients x length features, C (C + 1) / 2 sums")
+    L.check(L.lib().sa_freq_gram(_ptr(feats), int(n_clients), int(length), _ptr(out), C.c_void_p(_stream(feats))),
+            "sa_freq_gram")
+    return out

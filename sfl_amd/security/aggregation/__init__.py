@@ -6,3 +6,4 @@ from .secure_aggregator import SecureAggregator  # noqa: F401
 from .sparse_plain_aggregator import SparsePlainAggregator  # noqa: F401
 from .flame_aggregator import FlameAggregator  # noqa: F401
 from .mars_aggregator import MarsAggregator  # noqa: F401
+from .freq_aggregator import FreqAggregator  # noqa: F401

@@ -228,6 +228,53 @@ def mars_host(data: Sequence[Sequence[np.ndarray]], weights=None, threshold: flo
     return [combine_host([xs[i] for i in kept], [w[i] for i in kept]) for xs in layers], report
 
 
+def upload(layers: list, dev, who: str) -> list:
+    """``layers[l][i]`` as flat contiguous tensors on ``dev``: at most 16
+    clients; a host layer among device ones goes there through pinned memory."""
+    from ... import hostpipe as H
+
+    C = len(layers[0])
+    if C > MAX_DEVICE_CLIENTS:
+        raise NotImplementedError(f"{who} takes at most {MAX_DEVICE_CLIENTS} clients on the device "
+                                  f"(SA_FLAME_MAX_CLIENTS), got {C}; the host form takes any number")
+    on_dev = []
+    for l, xs in enumerate(layers):
+        row = []
+        for i, x in enumerate(xs):
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                if x.device != dev:
+                    raise ValueError(f"layer {l}, client {i}: on {x.device}, the others on {dev}")
+                row.append(x.detach().contiguous().reshape(-1))
+            else:  # a host layer among device ones: through pinned memory
+                row.append(H.h2d(x, dev).reshape(-1))
+        on_dev.append(row)
+    return on_dev
+
+
+def average_kept(layers: list, on_dev: list, w: List[float], keep: List[bool], dev) -> list:
+    """Step 4 on the device over ``upload``'s tensors: float64 layers in the uploads' shapes."""
+    from ... import hostpipe as H
+    from ... import kernels as K
+
+    C = len(layers[0])
+    kept_w = [w[i] for i in range(C) if keep[i]]
+    W = float(np.asarray(kept_w, np.float64).sum())
+    if W == 0.0:
+        raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+    zero = torch.zeros(max(row[0].numel() for row in on_dev), dtype=on_dev[0][0].dtype, device=dev)
+    outs = []
+    for xs, row in zip(layers, on_dev):
+        n = row[0].numel()
+        if n <= 1:  # np.average itself (flame_aggregator's step 4), on a copy of at most one element
+            host = combine_host([H.d2h(row[i], pooled=False) for i in range(C) if keep[i]], kept_w)
+            outs.append(H.h2d(host, dev).reshape(tuple(xs[0].shape)))
+            continue
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        K.flame_combine(row, [1.0] * C, w, keep, zero[:n], W, out)
+        outs.append(out.reshape(tuple(xs[0].shape)))
+    return outs
+
+
 class MarsAggregator(FlameAggregator):
     """MARS aggregator (Lipschitz-based Byzantine-robust aggregation).
 
@@ -290,23 +337,9 @@ class MarsAggregator(FlameAggregator):
 
     def _device_average(self, layers: list, w: List[float], dev) -> list:
         from ... import hostpipe as H
-        from ... import kernels as K
 
+        on_dev = upload(layers, dev, "MarsAggregator")
         C = len(layers[0])
-        if C > MAX_DEVICE_CLIENTS:
-            raise NotImplementedError(f"MarsAggregator takes at most {MAX_DEVICE_CLIENTS} clients on the device "
-                                      f"(SA_FLAME_MAX_CLIENTS), got {C}; the host form takes any number")
-        on_dev = []
-        for l, xs in enumerate(layers):
-            row = []
-            for i, x in enumerate(xs):
-                if isinstance(x, torch.Tensor) and x.is_cuda:
-                    if x.device != dev:
-                        raise ValueError(f"layer {l}, client {i}: on {x.device}, the others on {dev}")
-                    row.append(x.detach().contiguous().reshape(-1))
-                else:  # a host layer among device ones: through pinned memory
-                    row.append(H.h2d(x, dev).reshape(-1))
-            on_dev.append(row)
         plan = clp_plan([tuple(xs[0].shape) for xs in layers])
         if plan:
             feats, host_layers = self._device_features(layers, on_dev, plan, dev)
@@ -319,22 +352,7 @@ class MarsAggregator(FlameAggregator):
         keep = [lb == 0 for lb in report["labels"]]
         if not any(keep):
             return [row[0].clone().reshape(tuple(xs[0].shape)) for xs, row in zip(layers, on_dev)]
-        kept_w = [w[i] for i in range(C) if keep[i]]
-        W = float(np.asarray(kept_w, np.float64).sum())
-        if W == 0.0:
-            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
-        zero = torch.zeros(max(row[0].numel() for row in on_dev), dtype=on_dev[0][0].dtype, device=dev)
-        outs = []
-        for xs, row in zip(layers, on_dev):
-            n = row[0].numel()
-            if n <= 1:  # np.average itself (flame_aggregator's step 4), on a copy of at most one element
-                host = combine_host([H.d2h(row[i], pooled=False) for i in range(C) if keep[i]], kept_w)
-                outs.append(H.h2d(host, dev).reshape(tuple(xs[0].shape)))
-                continue
-            out = torch.empty(n, dtype=torch.float64, device=dev)
-            K.flame_combine(row, [1.0] * C, w, keep, zero[:n], W, out)
-            outs.append(out.reshape(tuple(xs[0].shape)))
-        return outs
+        return average_kept(layers, on_dev, w, keep, dev)
 
     def _average(self, parties: list, weights):
         single = not isinstance(parties[0], (list, tuple))
