@@ -1065,6 +1065,32 @@ int sa_mars_sigma(const void* const* w, int n_clients, int x_type, uint64_t n_ma
 int sa_mars_bn(const void* const* bn_w, const void* const* bn_var, int n_clients, int x_type, uint64_t n_bn,
                double* out, void* stream);
 
+/* sa_mars_sigma_wide: sa_mars_sigma for p = min(rows, cols) in          */
+/* 1..SA_MARS_WIDE_MAX_P (a hidden fc layer, a 5x5 or 7x7 conv with more */
+/* than 32 input channels); the arguments, out's layout, the BatchNorm   */
+/* scale and the rules for an all-zero matrix (+0.0) and a NaN or an     */
+/* infinity (a non-finite value for that matrix) are sa_mars_sigma's.    */
+/* Two kernels: the float64 Gram matrix X X^T of every (client, matrix)  */
+/* into scratch, in 64 x 64 tiles of its upper triangle on               */
+/* v_mfma_f64_16x16x4_f64 (the operands converted first), then one block */
+/* a matrix: Householder reduction to tridiagonal form in place and the  */
+/* largest eigenvalue by Sturm counts, sectioned until the interval      */
+/* cannot be split in float64.  The order of every sum is a function of  */
+/* the shapes: the same input gives the same bits.  scratch:             */
+/* sa_mars_wide_scratch_bytes = n_clients n_mat p p 8 bytes, 8-byte      */
+/* aligned, overwritten.  p outside 1..SA_MARS_WIDE_MAX_P and a scratch  */
+/* size above 2^31 - 1 are refused with SA_ERR_UNSUPPORTED and nothing   */
+/* is computed (sa_mars_wide_scratch_bytes returns the same negative     */
+/* code); everything else as above, a null or misaligned scratch         */
+/* included.  Empty calls look at no pointer.  ABI version 3 (additive). */
+#define SA_MARS_WIDE_MAX_P 512
+
+int sa_mars_wide_scratch_bytes(int n_clients, uint64_t n_mat, uint64_t rows, uint64_t cols);
+
+int sa_mars_sigma_wide(const void* const* w, int n_clients, int x_type, uint64_t n_mat, uint64_t rows, uint64_t cols,
+                       const void* const* bn_w, const void* const* bn_var, uint64_t n_bn, void* scratch, double* out,
+                       void* stream);
+
 /* ------------------------------------------------------------------ */
 /* FreqAggregator: the features of the reference's FreqFed robust       */
 /* aggregator (examples/security/h_bd/agg_freqfed.py) for C clients,    */

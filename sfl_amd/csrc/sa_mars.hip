@@ -34,6 +34,39 @@
 // A non-finite trace (a NaN or an infinity in the matrix, or an overflowing
 // square) skips the sweeps: the value is sqrt(trace), NaN or +inf.
 // No atomics, no data-dependent grid: the same input gives the same bits.
+//
+// sigma of a wider layer (32 < p <= SA_MARS_WIDE_MAX_P; sa_mars_sigma_wide
+// takes every p from 1): two kernels over a p x p float64 matrix a (client,
+// matrix) in the caller's scratch.
+//   k_gram_wide  G = X X^T.  A block of four waves (2 x 2) per 64 x 64 tile of
+//      the upper triangle of G, a wave 2 x 2 accumulators of
+//      v_mfma_f64_16x16x4_f64; k advances 16 a step through double-buffered
+//      64 x 16 panels in LDS (sa_freq.hip's k_gemm: row stride 18 doubles, one
+//      barrier a step).  Both panels come from X: a tile on the diagonal
+//      stages and reads one, a tile off it stages two and is stored on both
+//      sides of the diagonal; tiles below it have no block.  The staging
+//      thread's (row, k) follows X's contiguous dimension.  No split along k.
+//   k_eig_wide   one block of four waves a matrix, no grid-wide step:
+//      1. the trace; not finite or not positive: sqrt(trace) is the value (NaN,
+//         +inf or +0.0).  Else G is scaled in place by the power of two that
+//         puts the trace in [1, 2): exact, and no square below can overflow.
+//      2. Householder reduction to tridiagonal form in place, column by
+//         column.  Column k's tail is read from row k (G is symmetric to the
+//         bit, and stays so) into v (LDS); w = beta G v over the trailing
+//         matrix with wave r on rows r, r + 4, ..., lane l on columns l,
+//         l + 64, ... (eight accumulators a lane, every load coalesced along
+//         a row), the waves' partial columns added in wave order through LDS;
+//         w -= (beta / 2)(v . w) v; the trailing rank-2 update in the same
+//         split.  Norms and dots: a thread's terms in index order, the wave's
+//         butterfly, the waves in order.  A tail that is zero below the
+//         subdiagonal takes no step.
+//      3. diagonal and off-diagonal in LDS, the Gershgorin interval, and the
+//         largest eigenvalue by Sturm counts in a multi-section: each of the
+//         256 threads counts at one shift of the interval, the interval
+//         becomes the gap around the first shift with every eigenvalue below
+//         it; it ends when no shift lies strictly inside, and the upper end
+//         is the eigenvalue.
+//      4. scaled back, the square root, the BatchNorm scale: k_sigma's lines.
 #include <hip/hip_runtime.h>
 
 #include "sa_compress.h"
@@ -280,6 +313,285 @@ __global__ void __launch_bounds__(wave::kBlock) k_bn(const Ptrs px, uint64_t n_b
   }
 }
 
+// --- wider layers: the Gram matrix in tiles --------------------------------------------
+constexpr int kWideMaxP = SA_MARS_WIDE_MAX_P;
+constexpr int kTile = 64;           // a block's tile of G: kTile x kTile
+constexpr int kStep = 16;           // k a step
+constexpr int kPanelLd = kStep + 2; // a panel's row stride in doubles (sa_freq.hip: 32-byte pieces tile the banks once)
+constexpr int kPanel = kTile * kPanelLd;
+constexpr double kTiny = 2.2250738585072014e-308;  // the smallest normal number
+
+typedef double double2 __attribute__((ext_vector_type(2)));
+
+// four doubles of a panel row: a row starts 16-byte aligned (kPanelLd is even), so two 16-byte accesses
+__device__ __forceinline__ void put4(double* p, double4 v) {
+  reinterpret_cast<double2*>(p)[0] = double2{v[0], v[1]};
+  reinterpret_cast<double2*>(p)[1] = double2{v[2], v[3]};
+}
+__device__ __forceinline__ double4 get4(const double* p) {
+  const double2 lo = reinterpret_cast<const double2*>(p)[0], hi = reinterpret_cast<const double2*>(p)[1];
+  return double4{lo[0], lo[1], hi[0], hi[1]};
+}
+
+// X[row][k .. k + 3], zero outside p x K
+template <class T>
+__device__ __forceinline__ double4 fetch4(const T* __restrict__ x, uint64_t row, uint64_t k, int p, uint64_t K,
+                                          uint64_t si, uint64_t sk) {
+  double4 v = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < 4; s++) v[s] = x_at(x, row, k + s, p, K, si, sk);
+  return v;
+}
+
+// grid (n_clients * n_mat, tiles (tiles + 1) / 2): blockIdx.y counts the tiles (ti, tj), tj >= ti, row by row.
+// G of (client c, matrix m) = scratch + (c n_mat + m) p p, row-major, both triangles written.
+template <class T>
+__global__ void __launch_bounds__(wave::kBlock) k_gram_wide(const Ptrs px, uint64_t n_mat, int p, uint64_t K,
+                                                            uint64_t si, uint64_t sk, uint64_t mat_elems, int tiles,
+                                                            double* __restrict__ scratch) {
+  __shared__ __attribute__((aligned(16))) double xs[2 * kPanel];
+  __shared__ __attribute__((aligned(16))) double ys[2 * kPanel];
+  const uint64_t cm = blockIdx.x, c = cm / n_mat, m = cm - c * n_mat;
+  int ti = 0, rest = blockIdx.y;
+  while (rest >= tiles - ti) rest -= tiles - ti, ti++;
+  const bool diag = rest == 0;  // (block-uniform)
+  const uint64_t i0 = (uint64_t)ti * kTile, j0 = (uint64_t)(ti + rest) * kTile;
+  const T* x = reinterpret_cast<const T*>(px.w[c]) + m * mat_elems;
+  double* G = scratch + cm * (uint64_t)p * (uint64_t)p;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int li = lane & 15, g = lane >> 4, wr = w >> 1, wc = w & 1;
+  // staging: thread t moves four k of one row of either panel; consecutive threads along X's contiguous dimension
+  const int srow = sk == 1 ? t >> 2 : t & 63, sk0 = (sk == 1 ? t & 3 : t >> 6) * 4;
+  const double* bs = diag ? xs : ys;  // a diagonal tile's second operand is its first panel
+
+  double4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; a++)
+#pragma unroll
+    for (int b = 0; b < 2; b++) acc[a][b] = double4{0.0, 0.0, 0.0, 0.0};
+
+  double4 vx = fetch4(x, i0 + srow, (uint64_t)sk0, p, K, si, sk), vy = vx;
+  if (!diag) vy = fetch4(x, j0 + srow, (uint64_t)sk0, p, K, si, sk);
+  put4(&xs[srow * kPanelLd + sk0], vx);
+  if (!diag) put4(&ys[srow * kPanelLd + sk0], vy);
+  __syncthreads();
+  const uint64_t steps = (K + kStep - 1) / kStep;
+  for (uint64_t st = 0; st < steps; st++) {
+    const int cur = (int)(st & 1) * kPanel, nxt = kPanel - cur;
+    const bool more = st + 1 < steps;
+    if (more) {
+      vx = fetch4(x, i0 + srow, (st + 1) * kStep + sk0, p, K, si, sk);
+      if (!diag) vy = fetch4(x, j0 + srow, (st + 1) * kStep + sk0, p, K, si, sk);
+    }
+    double4 a[2], b[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      a[h] = get4(&xs[cur + (32 * wr + 16 * h + li) * kPanelLd + 4 * g]);
+      b[h] = get4(&bs[cur + (32 * wc + 16 * h + li) * kPanelLd + 4 * g]);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; s++)
+#pragma unroll
+      for (int ha = 0; ha < 2; ha++)
+#pragma unroll
+        for (int hb = 0; hb < 2; hb++)
+          acc[ha][hb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ha][s], b[hb][s], acc[ha][hb], 0, 0, 0);
+    if (more) {
+      put4(&xs[nxt + srow * kPanelLd + sk0], vx);
+      if (!diag) put4(&ys[nxt + srow * kPanelLd + sk0], vy);
+    }
+    __syncthreads();
+  }
+  // register r of lane group g: the 16 x 16 tile's element (4 r + g, li); G[i][j] and G[j][i] are the same
+  // products in the same order of k, so a diagonal tile is symmetric to the bit without a mirrored store
+#pragma unroll
+  for (int ha = 0; ha < 2; ha++)
+#pragma unroll
+    for (int hb = 0; hb < 2; hb++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const uint64_t i = i0 + 32 * wr + 16 * ha + 4 * r + g, j = j0 + 32 * wc + 16 * hb + li;
+        if (i < (uint64_t)p && j < (uint64_t)p) {
+          G[i * p + j] = acc[ha][hb][r];
+          if (!diag) G[j * p + i] = acc[ha][hb][r];
+        }
+      }
+}
+
+// --- wider layers: the largest eigenvalue -------------------------------------------------
+// The block's reduction in a fixed order: the wave's butterfly, then the waves
+// in order; every thread gets the result.  red: kWaves doubles of LDS.
+template <class Op>
+__device__ __forceinline__ double block_reduce(double v, double* red, Op op) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, kWave));
+  __syncthreads();  // the last call's readers are done with red
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return op(op(op(red[0], red[1]), red[2]), red[3]);
+}
+struct Add {
+  __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
+};
+struct Min {
+  __device__ __forceinline__ double operator()(double a, double b) const { return b < a ? b : a; }
+};
+struct Max {
+  __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; }
+};
+
+constexpr int kCols = kWideMaxP / kWave;  // a lane's columns of a trailing row
+constexpr int kSections = wave::kBlock;   // shifts a round of the multi-section
+constexpr int kMaxRounds = 80;            // far above what 2^-1074 of an interval takes; the loop ends before it
+
+// how many eigenvalues of the tridiagonal matrix (d, e2 = e^2) lie below x
+__device__ __forceinline__ int sturm(const double* d, const double* e2, int p, double x) {
+  double q = d[0] - x;
+  if (q == 0.0) q = kTiny;
+  int below = q < 0.0;
+  for (int i = 1; i < p; i++) {
+    q = (d[i] - x) - e2[i - 1] / q;
+    if (q == 0.0) q = kTiny;
+    below += q < 0.0;
+  }
+  return below;
+}
+
+template <class T>
+__global__ void __launch_bounds__(wave::kBlock) k_eig_wide(const Ptrs px, uint64_t n_mat, int p, uint64_t n_bn,
+                                                           double* __restrict__ scratch, double* __restrict__ out) {
+  __shared__ double v[kWideMaxP], w[kWideMaxP], d[kWideMaxP], e[kWideMaxP];
+  __shared__ double part[wave::kWaves * kWideMaxP];  // the waves' partial columns; then the round's shifts
+  __shared__ int full[kSections];
+  __shared__ double red[wave::kWaves];
+  const uint64_t cm = blockIdx.x, c = cm / n_mat, m = cm - c * n_mat;
+  double* G = scratch + cm * (uint64_t)p * (uint64_t)p;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+
+  double tr = 0.0;
+  for (int i = t; i < p; i += wave::kBlock) tr += G[(uint64_t)i * p + i];
+  const double trace = block_reduce(tr, red, Add());
+  double lambda = trace;  // NaN, +inf, or nothing to find: k_sigma's rule
+  if (trace > 0.0 && trace <= 1.79769313486231570815e308) {  // (block-uniform: every thread has the same sum)
+    const int ex = ilogb(trace);
+    for (int idx = t; idx < p * p; idx += wave::kBlock) G[idx] = ldexp(G[idx], -ex);
+    __syncthreads();
+
+    // --- Householder: column k's tail x = G[k][k + 1 ..] becomes (alpha, 0, ...) ---
+    for (int k = 0; k + 2 < p; k++) {
+      const int L = p - k - 1;  // the trailing matrix: L x L from (k + 1, k + 1)
+      double* A = G + (uint64_t)(k + 1) * p + (k + 1);
+      double s2 = 0.0;
+      for (int j = t; j < L; j += wave::kBlock) {
+        const double xj = G[(uint64_t)k * p + k + 1 + j];
+        v[j] = xj;
+        if (j) s2 += xj * xj;
+      }
+      s2 = block_reduce(s2, red, Add());
+      const double x0 = v[0];
+      if (s2 < kTiny) {  // nothing below the subdiagonal (block-uniform): no step
+        if (t == 0) d[k] = G[(uint64_t)k * p + k], e[k] = x0;
+      } else {
+        const double norm = sqrt(x0 * x0 + s2), alpha = x0 >= 0.0 ? -norm : norm, v0 = x0 - alpha;
+        const double beta = 2.0 / (v0 * v0 + s2);
+        __syncthreads();  // every thread has read x0
+        if (t == 0) v[0] = v0, d[k] = G[(uint64_t)k * p + k], e[k] = alpha;
+        __syncthreads();
+        // w = beta A v: wave wv's rows, lane's columns; A is symmetric, so a column's sum over rows is a row's
+        double acc[kCols], vj[kCols], wj[kCols];
+#pragma unroll
+        for (int cc = 0; cc < kCols; cc++) acc[cc] = 0.0;
+        for (int i = wv; i < L; i += wave::kWaves) {
+          const double vi = v[i];
+          const double* row = A + (uint64_t)i * p;
+#pragma unroll
+          for (int cc = 0; cc < kCols; cc++) {
+            const int j = lane + kWave * cc;
+            if (j < L) acc[cc] += row[j] * vi;
+          }
+        }
+#pragma unroll
+        for (int cc = 0; cc < kCols; cc++) {
+          const int j = lane + kWave * cc;
+          if (j < L) part[wv * kWideMaxP + j] = acc[cc];
+        }
+        __syncthreads();
+        double dot = 0.0;
+        for (int j = t; j < L; j += wave::kBlock) {
+          const double wj0 = beta * (((part[j] + part[kWideMaxP + j]) + part[2 * kWideMaxP + j]) + part[3 * kWideMaxP + j]);
+          w[j] = wj0;
+          dot += v[j] * wj0;
+        }
+        dot = block_reduce(dot, red, Add());
+        const double half = 0.5 * beta * dot;
+        for (int j = t; j < L; j += wave::kBlock) w[j] = w[j] - half * v[j];
+        __syncthreads();
+        // A -= v w^T + w v^T: (i, j) and (j, i) get the same two products, added in either order
+#pragma unroll
+        for (int cc = 0; cc < kCols; cc++) {
+          const int j = lane + kWave * cc;
+          vj[cc] = j < L ? v[j] : 0.0, wj[cc] = j < L ? w[j] : 0.0;
+        }
+        for (int i = wv; i < L; i += wave::kWaves) {
+          const double vi = v[i], wi = w[i];
+          double* row = A + (uint64_t)i * p;
+#pragma unroll
+          for (int cc = 0; cc < kCols; cc++) {
+            const int j = lane + kWave * cc;
+            if (j < L) row[j] = row[j] - (vi * wj[cc] + wi * vj[cc]);
+          }
+        }
+      }
+      __syncthreads();  // the trailing matrix and v, w before the next column
+    }
+    if (t == 0) {
+      d[p - 1] = G[(uint64_t)(p - 1) * p + p - 1];
+      if (p > 1) d[p - 2] = G[(uint64_t)(p - 2) * p + p - 2], e[p - 2] = G[(uint64_t)(p - 2) * p + p - 1];
+    }
+    __syncthreads();
+
+    // --- the Gershgorin interval, e^2 into w ---
+    double lo = 1.79769313486231570815e308, hi = -lo;
+    for (int i = t; i < p; i += wave::kBlock) {
+      const double r = (i ? fabs(e[i - 1]) : 0.0) + (i + 1 < p ? fabs(e[i]) : 0.0);
+      lo = Min()(lo, d[i] - r), hi = Max()(hi, d[i] + r);
+      if (i + 1 < p) w[i] = e[i] * e[i];
+    }
+    lo = block_reduce(lo, red, Min());
+    hi = block_reduce(hi, red, Max());  // (its barriers publish w)
+
+    // --- the multi-section: the upper end keeps every eigenvalue at or below it ---
+    double* shift = part;
+    for (int round = 0; round < kMaxRounds; round++) {
+      const double xt = lo + (hi - lo) * (1.0 / (kSections + 1)) * (double)(t + 1);
+      const bool inside = lo < xt && xt < hi;
+      shift[t] = xt;
+      full[t] = inside ? (sturm(d, w, p, xt) == p ? 2 : 1) : 0;  // 0: no shift of its own
+      __syncthreads();
+      // every thread walks the shifts in order: the last one below the top eigenvalue, the first one above
+      double nlo = lo, nhi = hi;
+      bool any = false;
+      for (int s = 0; s < kSections; s++) {
+        const int f = full[s];
+        const double xs = shift[s];
+        any |= f != 0;
+        if (f == 1 && xs > nlo && xs < nhi) nlo = xs;
+        if (f == 2 && xs < nhi) nhi = xs;
+      }
+      lo = nlo, hi = nhi;  // (the shifts ascend with s, so nlo < nhi whatever the counts say)
+      __syncthreads();  // the shifts are read before the next round's
+      if (!any) break;  // (block-uniform) the interval cannot be split further
+    }
+    lambda = ldexp(hi, ex);
+  }
+  if (t == 0) {
+    double sigma = sqrt(lambda > 0.0 || lambda != lambda ? lambda : 0.0);
+    if (m < n_bn)
+      sigma = sigma * bn_scale(reinterpret_cast<const T*>(px.bn_w[c]), reinterpret_cast<const T*>(px.bn_var[c]), m);
+    out[cm] = sigma;
+  }
+}
+
 // the table of one argument: required, element-aligned device pointers
 static int take_table(const void* const* t, int n_clients, uintptr_t esz, const void** into, const char* what,
                       const char* name) {
@@ -305,10 +617,78 @@ static int check_clients(int n_clients, const char* what) {
   return SA_OK;
 }
 
+// the scalars of a wide call; *bytes gets the scratch's size
+static int check_wide(int n_clients, uint64_t n_mat, uint64_t rows, uint64_t cols, const char* what, uint64_t* bytes) {
+  int rc = check_clients(n_clients, what);
+  if (rc == SA_OK) rc = check_n(n_mat, 24, what, " matrices (n_mat)");
+  if (rc == SA_OK) rc = check_n(rows | cols, 24, what, " (rows, cols)");
+  if (rc != SA_OK) return rc;
+  const uint64_t p = rows < cols ? rows : cols;
+  if (p < 1 || p > (uint64_t)kWideMaxP) {
+    sa_set_error("%s: min(rows, cols) must be in 1..%d (SA_MARS_WIDE_MAX_P), got %llu", what, kWideMaxP,
+                 (unsigned long long)p);
+    return SA_ERR_UNSUPPORTED;
+  }
+  *bytes = (uint64_t)n_clients * n_mat * p * p * 8;  // (below 2^4 * 2^24 * 2^18 * 2^3)
+  if (*bytes > 0x7fffffffull) {
+    sa_set_error("%s: %d clients of %llu matrices with a smaller side of %llu need %llu bytes of scratch, above "
+                 "2^31 - 1", what, n_clients, (unsigned long long)n_mat, (unsigned long long)p,
+                 (unsigned long long)*bytes);
+    return SA_ERR_UNSUPPORTED;
+  }
+  return SA_OK;
+}
+
 }  // namespace mars
 }  // namespace sa
 
 using namespace sa::mars;
+
+extern "C" int sa_mars_wide_scratch_bytes(int n_clients, uint64_t n_mat, uint64_t rows, uint64_t cols) {
+  uint64_t bytes = 0;
+  const int rc = check_wide(n_clients, n_mat, rows, cols, "sa_mars_wide_scratch_bytes", &bytes);
+  return rc != SA_OK ? rc : (int)bytes;
+}
+
+extern "C" int sa_mars_sigma_wide(const void* const* w, int n_clients, int x_type, uint64_t n_mat, uint64_t rows,
+                                  uint64_t cols, const void* const* bn_w, const void* const* bn_var, uint64_t n_bn,
+                                  void* scratch, double* out, void* stream) {
+  const char* what = "sa_mars_sigma_wide";
+  uint64_t bytes = 0;
+  int rc = check_float(x_type, what);
+  if (rc == SA_OK) rc = check_wide(n_clients, n_mat, rows, cols, what, &bytes);
+  if (rc != SA_OK) return rc;
+  if (n_bn && (!bn_w || !bn_var)) {
+    sa_set_error("%s: bad arguments (bn_w and bn_var are required with n_bn)", what);
+    return SA_ERR_ARG;
+  }
+  if (n_clients == 0 || n_mat == 0) return SA_OK;
+  if (!out || misaligned(out, 8) || !scratch || misaligned(scratch, 8)) {
+    sa_set_error("%s: bad arguments (scratch and out are required, 8-byte aligned)", what);
+    return SA_ERR_ARG;
+  }
+  const uintptr_t esz = elem_size(x_type);
+  Ptrs px = {};
+  rc = take_table(w, n_clients, esz, px.w, what, "w");
+  if (rc == SA_OK && n_bn) rc = take_table(bn_w, n_clients, esz, px.bn_w, what, "bn_w");
+  if (rc == SA_OK && n_bn) rc = take_table(bn_var, n_clients, esz, px.bn_var, what, "bn_var");
+  if (rc != SA_OK) return rc;
+  const uint64_t p = rows < cols ? rows : cols, K = rows < cols ? cols : rows;
+  const uint64_t si = rows < cols ? cols : 1, sk = rows < cols ? 1 : cols;
+  const int tiles = (int)((p + kTile - 1) / kTile);
+  // (the scratch's bound keeps n_mat * n_clients below 2^28)
+  const unsigned mats = (unsigned)(n_mat * (uint64_t)n_clients);
+  hipStream_t st = (hipStream_t)stream;
+  dispatch_float(x_type, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((k_gram_wide<T>), dim3(mats, (unsigned)(tiles * (tiles + 1) / 2)), dim3(sa::wave::kBlock), 0, st,
+                       px, n_mat, (int)p, K, si, sk, rows * cols, tiles, reinterpret_cast<double*>(scratch));
+    hipLaunchKernelGGL((k_eig_wide<T>), dim3(mats), dim3(sa::wave::kBlock), 0, st, px, n_mat, (int)p, n_bn,
+                       reinterpret_cast<double*>(scratch), out);
+  });
+  SA_HIP_CHECK(hipGetLastError());
+  return SA_OK;
+}
 
 extern "C" int sa_mars_sigma(const void* const* w, int n_clients, int x_type, uint64_t n_mat, uint64_t rows,
                              uint64_t cols, const void* const* bn_w, const void* const* bn_var, uint64_t n_bn,

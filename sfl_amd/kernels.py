@@ -1249,20 +1249,51 @@ def mars_sigma(ws: Sequence, n_mat: int, rows: int, cols: int, out: torch.Tensor
     channels) times ``|bn_w[m]| / sqrt(max(bn_var[m], 0) + 1e-5)`` for
     ``m < n_bn``.  ``min(rows, cols)`` above ``SA_MARS_MAX_P`` is refused by
     the library.  See sa_mars_sigma in include/sfl_sa.h."""
+    head, tail = _mars_sigma_args("mars_sigma", ws, n_mat, rows, cols, out, offset, bn_w, bn_var)
+    L.check(L.lib().sa_mars_sigma(*head, *tail), "sa_mars_sigma")
+    return out
+
+
+def _mars_sigma_args(what: str, ws: Sequence, n_mat: int, rows: int, cols: int, out: torch.Tensor, offset: int,
+                     bn_w: Sequence, bn_var: Sequence) -> tuple:
+    """What sa_mars_sigma and sa_mars_sigma_wide share: the arguments up to
+    ``n_bn``, and ``(out, stream)``."""
     c = len(ws)
-    like = _mars_like("mars_sigma", ws)
+    like = _mars_like(what, ws)
     if len(bn_w) != len(bn_var) or len(bn_w) not in (0, c):
-        raise ValueError("mars_sigma: bn_w and bn_var are one tensor per client each, or both empty")
+        raise ValueError(f"{what}: bn_w and bn_var are one tensor per client each, or both empty")
     n_bn = 0
     if len(bn_w):
-        first = _mars_like("mars_sigma", bn_w)
+        first = _mars_like(what, bn_w)
         n_bn = first.numel()
-    table = _mars_table("mars_sigma", "tensor", ws, n_mat * rows * cols, like)
-    tw = _mars_table("mars_sigma", "bn_w", bn_w, n_bn, like) if n_bn else None
-    tv = _mars_table("mars_sigma", "bn_var", bn_var, n_bn, like) if n_bn else None
-    L.check(L.lib().sa_mars_sigma(table, c, _XTYPE.get(like.dtype, -1), int(n_mat), int(rows), int(cols), tw, tv, n_bn,
-                                  _mars_out("mars_sigma", out, offset, c * n_mat), C.c_void_p(_stream(like))),
-            "sa_mars_sigma")
+    table = _mars_table(what, "tensor", ws, n_mat * rows * cols, like)
+    tw = _mars_table(what, "bn_w", bn_w, n_bn, like) if n_bn else None
+    tv = _mars_table(what, "bn_var", bn_var, n_bn, like) if n_bn else None
+    return ((table, c, _XTYPE.get(like.dtype, -1), int(n_mat), int(rows), int(cols), tw, tv, n_bn),
+            (_mars_out(what, out, offset, c * n_mat), C.c_void_p(_stream(like))))
+
+
+def mars_wide_scratch_bytes(n_clients: int, n_mat: int, rows: int, cols: int) -> int:
+    """Bytes of device scratch ``mars_sigma_wide`` needs; a size the library
+    does not take raises ``SALibraryError`` with code ``SA_ERR_UNSUPPORTED``."""
+    rc = L.lib().sa_mars_wide_scratch_bytes(int(n_clients), int(n_mat), int(rows), int(cols))
+    if rc < 0:
+        L.check(rc, "sa_mars_wide_scratch_bytes")
+    return rc
+
+
+def mars_sigma_wide(ws: Sequence, n_mat: int, rows: int, cols: int, scratch: torch.Tensor, out: torch.Tensor,
+                    offset: int = 0, *, bn_w: Sequence = (), bn_var: Sequence = ()) -> torch.Tensor:
+    """``mars_sigma`` for ``min(rows, cols)`` up to ``SA_MARS_WIDE_MAX_P``,
+    through ``scratch`` (``mars_wide_scratch_bytes`` bytes on the same device,
+    overwritten).  See sa_mars_sigma_wide in include/sfl_sa.h."""
+    head, tail = _mars_sigma_args("mars_sigma_wide", ws, n_mat, rows, cols, out, offset, bn_w, bn_var)
+    _require_gpu(scratch)
+    if not scratch.is_contiguous() or scratch.device != out.device:
+        raise ValueError("mars_sigma_wide: scratch is contiguous, on out's device")
+    _require_scratch("mars_sigma_wide", scratch, mars_wide_scratch_bytes(len(ws), n_mat, rows, cols),
+                     "mars_wide_scratch_bytes(n_clients, n_mat, rows, cols)")
+    L.check(L.lib().sa_mars_sigma_wide(*head, _ptr(scratch), *tail), "sa_mars_sigma_wide")
     return out
 
 

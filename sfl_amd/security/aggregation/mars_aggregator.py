@@ -70,8 +70,13 @@ reference's behaviour, reproduced here.
 Weights are one finite scalar per client (``None``: 1.0 each).  On the device
 a layer whose smaller side exceeds ``SA_MARS_MAX_P`` (32), such as a hidden fc
 layer, is read to the host and takes ``np.linalg.svd`` there
-(``last_report["host_layers"]`` counts them), and at most 16 clients are
-taken; the host form takes any number.
+(``last_report["host_layers"]`` counts them) -- or, with
+``wide_layers="device"``, stays on the device up to a smaller side of
+``SA_MARS_WIDE_MAX_P`` (512) and takes ``sa_mars_sigma_wide`` (a tiled float64
+Gram matrix, Householder reduction and Sturm counts;
+``last_report["wide_layers"]`` counts them, and only what is beyond that limit
+still goes to the host).  At most 16 clients are taken on the device; the host
+form takes any number.
 """
 
 from __future__ import annotations
@@ -86,6 +91,7 @@ from ...device import PYU
 from .flame_aggregator import MAX_DEVICE_CLIENTS, FlameAggregator, _layers, _np_dtype, _weights
 
 MAX_P = 32  # SA_MARS_MAX_P: the Gram matrix of the smaller side lives in one wave's LDS
+WIDE_MAX_P = 512  # SA_MARS_WIDE_MAX_P: the Gram matrix in scratch, one block a matrix
 EPS = 1e-5
 TOP = 0.05
 
@@ -290,20 +296,30 @@ class MarsAggregator(FlameAggregator):
     After each ``average``, ``last_report`` holds ``labels`` (0 kept, -1 left
     out), ``features`` (every client's kept Lipschitz constants),
     ``kept_counts``, ``distances`` and ``host_layers`` (the plan entries whose
-    features were computed on the host).
+    features were computed on the host); the device path adds ``wide_layers``
+    (the plan entries that took ``sa_mars_sigma_wide``).
+
+    ``wide_layers`` says where a layer with a smaller side above 32 goes on
+    the device path: ``"host"`` (the default) reads it to the host for LAPACK,
+    ``"device"`` keeps it on the device up to a smaller side of 512.
 
     Examples:
       >>> aggregator = MarsAggregator(server, anomaly_threshold=1.0)
       >>> fl = FLModel(server=server, device_list=clients, model=build, aggregator=aggregator)
     """
 
-    def __init__(self, device: PYU, anomaly_threshold: float = 1.0):
+    def __init__(self, device: PYU, anomaly_threshold: float = 1.0, wide_layers: str = "host"):
         super().__init__(device)
+        if wide_layers not in ("host", "device"):
+            raise ValueError(f"wide_layers is 'host' or 'device', not {wide_layers!r}")
         self.anomaly_threshold = anomaly_threshold
+        self.wide_layers = wide_layers
 
     # ------------------------------------------------------------ the paths
     def _device_features(self, layers: list, on_dev: list, plan: list, dev) -> tuple:
-        """Every client's arrays of step 2 and the number of plan entries that went to the host."""
+        """Every client's arrays of step 2 and the numbers of plan entries that went to the host and to the
+        wide kernels."""
+        from ... import _lib as L
         from ... import hostpipe as H
         from ... import kernels as K
 
@@ -312,28 +328,38 @@ class MarsAggregator(FlameAggregator):
         sizes = [shapes[idx][0] if kind != "fc" else 1 for kind, idx in plan]
         offsets = np.concatenate([[0], np.cumsum([C * n for n in sizes])]).astype(int)
         buf = torch.zeros(int(offsets[-1]), dtype=torch.float64, device=dev)
+        dims = {e: (shapes[idx][0], shapes[idx][1], int(np.prod(shapes[idx][2:]))) if kind == "conv"
+                else (1,) + shapes[idx] for e, (kind, idx) in enumerate(plan) if kind != "bn"}
+        # the entries for sa_mars_sigma_wide, and one scratch for the largest of them, reused in stream order
+        wide = {}
+        for e, (n_mat, rows, cols) in dims.items():
+            if self.wide_layers == "device" and n_mat and MAX_P < min(rows, cols) <= WIDE_MAX_P:
+                need = L.lib().sa_mars_wide_scratch_bytes(C, n_mat, rows, cols)
+                if need >= 0:  # (a size the library refuses: to the host like a wider one)
+                    wide[e] = need
+        scratch = torch.empty(max(wide.values()) // 8, dtype=torch.float64, device=dev) if wide else None
         on_host = {}
         for e, (kind, idx) in enumerate(plan):
             off = int(offsets[e])
             if kind == "bn":
                 K.mars_bn(on_dev[idx], on_dev[idx + 3], buf, off)
                 continue
-            s = shapes[idx]
-            n_mat, rows = (s[0], s[1]) if kind == "conv" else (1, s[0])
-            cols = int(np.prod(s[2:])) if kind == "conv" else s[1]
+            n_mat, rows, cols = dims[e]
             bn = _bn_of(plan, e) if kind == "conv" else None
-            if not 1 <= min(rows, cols) <= MAX_P or n_mat == 0:
-                # beyond the kernel's size: this entry's layers through pinned memory, LAPACK on the host
+            scale = dict(bn_w=on_dev[bn], bn_var=on_dev[bn + 3]) if bn is not None else {}
+            if e in wide:
+                K.mars_sigma_wide(on_dev[idx], n_mat, rows, cols, scratch, buf, off, **scale)
+            elif not 1 <= min(rows, cols) <= MAX_P or n_mat == 0:
+                # beyond the kernels' size: this entry's layers through pinned memory, LAPACK on the host
                 need = [idx] if bn is None else [idx, bn, bn + 3]
                 on_host[e] = [entry_host({l: H.d2h(on_dev[l][i], pooled=False).reshape(shapes[l]) for l in need},
                                          plan, e) for i in range(C)]
-                continue
-            K.mars_sigma(on_dev[idx], n_mat, rows, cols, buf, off, bn_w=on_dev[bn] if bn is not None else (),
-                         bn_var=on_dev[bn + 3] if bn is not None else ())
+            else:
+                K.mars_sigma(on_dev[idx], n_mat, rows, cols, buf, off, **scale)
         flat = H.d2h(buf, pooled=False) if buf.numel() else np.zeros(0)  # the one read of the features
         feats = [[on_host[e][i] if e in on_host else flat[offsets[e] + i * n:offsets[e] + (i + 1) * n]
                   for e, n in enumerate(sizes)] for i in range(C)]
-        return feats, len(on_host)
+        return feats, len(on_host), len(wide)
 
     def _device_average(self, layers: list, w: List[float], dev) -> list:
         from ... import hostpipe as H
@@ -342,12 +368,12 @@ class MarsAggregator(FlameAggregator):
         C = len(layers[0])
         plan = clp_plan([tuple(xs[0].shape) for xs in layers])
         if plan:
-            feats, host_layers = self._device_features(layers, on_dev, plan, dev)
+            feats, host_layers, wide_layers = self._device_features(layers, on_dev, plan, dev)
         else:  # the fallback's norms: every layer on the host
             hosts = [[H.d2h(row[i], pooled=False) for row in on_dev] for i in range(C)]
-            feats, host_layers = [features_host(h, plan) for h in hosts], len(layers)
+            feats, host_layers, wide_layers = [features_host(h, plan) for h in hosts], len(layers), 0
         report = decide(feats, plan, self.anomaly_threshold)
-        report["host_layers"] = host_layers
+        report["host_layers"], report["wide_layers"] = host_layers, wide_layers
         self.last_report = report
         keep = [lb == 0 for lb in report["labels"]]
         if not any(keep):

@@ -29,7 +29,19 @@ per-pass median, timed with device events.  One JSON line:
     float32 torch value; max_ratio_vs_host: the largest |hip - host| over the
     tests' tolerance (K p / 2 + 64 p + 8) 2^-53 of client 0.
 
+--wide measures sa_mars_sigma_wide instead (layers with a smaller side above
+32: WIDE_SHAPES below), one JSON line per layer and one for all four:
+
+* hip:   ``mars_sigma_wide`` per layer through one scratch tensor, as
+         ``MarsAggregator(wide_layers="device")`` issues it (both kernels;
+         their separate times come from a kernel trace of this command)
+* torch: ``torch.linalg.matrix_norm(ord=2)`` of the stacked float32 batch
+* host:  the parent's path for such a layer: ``hostpipe.d2h`` of every
+         client's layer and ``mars_aggregator.entry_host`` (LAPACK per matrix,
+         float64), all clients, timed once with a host clock, the copy included
+
 usage: python tools/mars_bench.py [--clients 8] [--reps 10] [--torch-reps 2] [--passes 3] [--gram mfma] [--out FILE]
+       python tools/mars_bench.py --wide [--clients 8] [--out profiles/mars/mars_wide_bench.jsonl]
 """
 import argparse
 import json
@@ -56,6 +68,87 @@ def resnet18_shapes(classes=10):
     return shapes + [(classes, 512), (classes,)]
 
 
+WIDE_SHAPES = [(128, 784), (512, 512), (512, 4608), (128, 64, 7, 7)]
+
+
+def wide(args):
+    """The --wide mode (the module docstring)."""
+    import numpy as np
+    import torch
+
+    from sfl_amd import _lib as L
+    from sfl_amd import hostpipe as H
+    from sfl_amd import kernels as K
+    from sfl_amd.security.aggregation import mars_aggregator as M
+
+    L.lib()
+    if not torch.cuda.is_available():
+        raise SystemExit("mars_bench: needs a GPU (no fallback)")
+    dev = torch.device("cuda", 0)
+    C = args.clients
+    g = torch.Generator(device=dev).manual_seed(11)
+    dims = [(s[0], s[1], s[2] * s[3]) if len(s) == 4 else (1,) + s for s in WIDE_SHAPES]
+    ws = [[(torch.randn(s, generator=g, device=dev) * 0.05).reshape(-1) for _ in range(C)] for s in WIDE_SHAPES]
+    stacked = [torch.stack(w).reshape((C * d[0],) + d[1:]) for w, d in zip(ws, dims)]
+    offs = np.concatenate([[0], np.cumsum([C * d[0] for d in dims])]).astype(int)
+    buf = torch.zeros(int(offs[-1]), dtype=torch.float64, device=dev)
+    scratch = torch.empty(max(K.mars_wide_scratch_bytes(C, *d) for d in dims) // 8, dtype=torch.float64, device=dev)
+    keep = {}
+
+    def hip(which):
+        for l in which:
+            K.mars_sigma_wide(ws[l], *dims[l], scratch, buf, int(offs[l]))
+
+    def torch_pass(which):
+        keep["t"] = [torch.linalg.matrix_norm(stacked[l], ord=2) for l in which]
+
+    def events(fn, which, reps):
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(which)
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    every = list(range(len(dims)))
+    hip(every), torch_pass(every)  # warm-up of both on these shapes
+    torch.cuda.synchronize()
+    got = H.d2h(buf, pooled=False)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    for which in [[l] for l in every] + [every]:
+        hs, ts = [], []
+        for _ in range(args.passes):
+            hs.append(events(hip, which, args.reps))
+            ts.append(events(torch_pass, which, args.torch_reps))
+        hip_ms, torch_ms = statistics.median(hs), statistics.median(ts)
+        host_ms, ratio = None, None
+        if not args.skip_host:
+            t0 = time.perf_counter()
+            feats = [[M.entry_host({0: H.d2h(ws[l][i], pooled=False).reshape(WIDE_SHAPES[l])},
+                                   [("conv" if dims[l][0] > 1 else "fc", 0)], 0) for i in range(C)] for l in which]
+            host_ms = (time.perf_counter() - t0) * 1e3
+            ratio = 0.0
+            for l, f in zip(which, feats):
+                p, k = min(dims[l][1:]), max(dims[l][1:])
+                want = np.concatenate(f)
+                mine = got[offs[l]:offs[l + 1]]
+                ratio = max(ratio, float(np.max(np.abs(mine - want) / want)) / ((k * p / 2 + 64 * p + 8) * 2.0 ** -53))
+        line = {"case": "wide", "layers": [list(WIDE_SHAPES[l]) for l in which], "dtype": "float32", "clients": C,
+                "hip_ms": round(hip_ms, 4), "torch_ms": round(torch_ms, 4),
+                "host_ms": None if host_ms is None else round(host_ms, 1),
+                "speedup_vs_torch": round(torch_ms / hip_ms, 3),
+                "speedup_vs_host": None if host_ms is None else round(host_ms / hip_ms, 2),
+                "hip_ms_passes": [round(x, 4) for x in hs], "torch_ms_passes": [round(x, 4) for x in ts],
+                "matrices": int(sum(C * dims[l][0] for l in which)), "max_ratio_vs_host": ratio,
+                "timer": "device events; host: perf_counter, d2h included", "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line), flush=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=8)
@@ -64,8 +157,12 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--gram", default="mfma")
     ap.add_argument("--skip-host", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mars", "mars_bench.jsonl"))
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "mars", "mars_wide_bench.jsonl" if args.wide else "mars_bench.jsonl")
+    if args.wide:
+        return wide(args)
     import numpy as np
     import torch
 
