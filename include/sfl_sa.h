@@ -1135,6 +1135,55 @@ int sa_freq_features(const void* const* w, int n_clients, int x_type, uint64_t r
 
 int sa_freq_gram(const double* feats, int n_clients, uint64_t len, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* FlameAggregator for SA_FLAME_MAX_CLIENTS < C <=                      */
+/* SA_FLAME_WIDE_MAX_CLIENTS clients (17..64): sa_flame_stats and       */
+/* sa_flame_combine with the work split differently.  The definition of */
+/* the median g, of the statistics with their packed layout for the     */
+/* actual C (C (C + 1) / 2 + C float64) and of the combine, the         */
+/* arguments, `accumulate`, n == 0 and the NaN weight of a dropped      */
+/* client are those entries', word for word (agg_flame.py:27-203; :61-73*/
+/* the median, :79-89 and :128-132 the update norms, :95-112 the Gram   */
+/* matrix, :141-168 the clipping, :181-187 np.average, :193-199 the     */
+/* noise term).  Only the order of summation is this path's own:        */
+/*   sa_flame_stats_wide  a block of four waves takes tiles of 128      */
+/*           elements, all C clients' rows of a tile staged once in LDS */
+/*           (each client element is read from memory once).  G is      */
+/*           formed on v_mfma_f64_16x16x4_f64 in the 16 x 16 tiles of   */
+/*           the upper triangle of the client count padded to 32 or 64  */
+/*           (the pad rows are zeros and touch only entries that are    */
+/*           never stored): a wave sums its quarter of every tile's     */
+/*           elements in index order, over the block's tiles in index   */
+/*           order; N[i] belongs to wave i % 4: a lane's elements in    */
+/*           index order, the lanes by one butterfly.  A block adds its */
+/*           four waves' sums in wave order into one partial in         */
+/*           scratch; a second kernel, one thread a statistic, adds the */
+/*           blocks in block order.  The grid is a function of n only.  */
+/*           No atomics: the same input gives the same bits on every    */
+/*           run.  scratch: sa_flame_wide_scratch_bytes bytes, 8-byte   */
+/*           aligned, rewritten by every call.                          */
+/*   sa_flame_combine_wide  one streaming pass with a run-time loop     */
+/*           over the kept clients in client order: bit for bit         */
+/*           sa_flame_combine's expression.                             */
+/* Other element types, n >= 2^32, a client count outside 17..64, null  */
+/* and misaligned pointers and a call that drops every client are       */
+/* refused before any launch.  16-byte aligned tensors take 16-byte     */
+/* accesses; others element accesses, and the same bits.  Nothing may   */
+/* alias an output.  Everything is stream-ordered, allocates nothing    */
+/* and never synchronises with the host.  ABI version 3 (additive).     */
+/* ------------------------------------------------------------------ */
+#define SA_FLAME_WIDE_MAX_CLIENTS 64
+
+/* bytes of device scratch sa_flame_stats_wide needs (the blocks' partial
+ * sums), or a negative SA_ERR_* code */
+int sa_flame_wide_scratch_bytes(uint64_t n, int n_clients, int x_type);
+
+int sa_flame_stats_wide(const void* const* x, int n_clients, int x_type, uint64_t n, void* median_out, void* scratch,
+                        double* stats, int accumulate, void* stream);
+
+int sa_flame_combine_wide(const void* const* x, const double* scale, const double* weight, int n_clients, int x_type,
+                          uint64_t n, const void* median, double divisor, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ SA_QUANT_ZERO_POINT, SA_QUANT_LSTM = 0, 1
 SA_KMEANS_MAX_K, SA_KMEANS_BINS, SA_KMEANS_BAD_CODE = 256, 4096, 1
 SA_KMEANS_STATE_BYTES, SA_KMEANS_STATE_C, SA_KMEANS_STATE_DONE = 4104, 3072, 4096
 SA_FLAME_MAX_CLIENTS = 16
+SA_FLAME_WIDE_MAX_CLIENTS = 64
 SA_MARS_MAX_P = 32
 SA_MARS_WIDE_MAX_P = 512
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
@@ -50,6 +51,7 @@ EXPORTED = (
     "sa_dequant_fp8",
     "sa_kmeans_scratch_bytes", "sa_kmeans_hist", "sa_kmeans_step", "sa_kmeans_labels", "sa_dequant_lut",
     "sa_flame_scratch_bytes", "sa_flame_stats", "sa_flame_combine",
+    "sa_flame_wide_scratch_bytes", "sa_flame_stats_wide", "sa_flame_combine_wide",
     "sa_mars_sigma", "sa_mars_bn", "sa_mars_wide_scratch_bytes", "sa_mars_sigma_wide",
     "sa_freq_scratch_bytes", "sa_freq_features", "sa_freq_gram",
     "sa_dp_perturb_secure_f32", "sa_chacha20_keystream", "sa_chacha20_blocks_host", "sa_hb_normals_f64",
@@ -188,6 +190,9 @@ def _declare(lib):
     lib.sa_flame_scratch_bytes.argtypes = [u64, i32, i32]
     lib.sa_flame_stats.argtypes = [P(C.c_void_p), i32, i32, u64, vp, vp, vp, i32, vp]
     lib.sa_flame_combine.argtypes = [P(C.c_void_p), P(C.c_double), P(C.c_double), i32, i32, u64, vp, dbl, vp, vp]
+    lib.sa_flame_wide_scratch_bytes.argtypes = lib.sa_flame_scratch_bytes.argtypes
+    lib.sa_flame_stats_wide.argtypes = lib.sa_flame_stats.argtypes
+    lib.sa_flame_combine_wide.argtypes = lib.sa_flame_combine.argtypes
     lib.sa_mars_sigma.argtypes = [P(C.c_void_p), i32, i32, u64, u64, u64, P(C.c_void_p), P(C.c_void_p), u64, vp, vp]
     lib.sa_mars_bn.argtypes = [P(C.c_void_p), P(C.c_void_p), i32, i32, u64, vp, vp]
     lib.sa_mars_wide_scratch_bytes.argtypes = [i32, u64, u64, u64]

@@ -1185,7 +1185,7 @@ def flame_stats(xs: Sequence, median_out: torch.Tensor, scratch: torch.Tensor, s
 
 
 def flame_combine(xs: Sequence, scales: Sequence[float], weights: Sequence[float], keep: Sequence[bool],
-                  median: torch.Tensor, divisor: float, out: torch.Tensor) -> torch.Tensor:
+                  median: torch.Tensor, divisor: float, out: torch.Tensor, *, _entry: str = "sa_flame_combine") -> torch.Tensor:
     """``out`` (float64) = the weighted average of the kept clients' clipped
     models ``median + (x - median) * scale``, divided by ``divisor``.  A
     client with ``keep[i]`` false crosses the C-ABI with a NaN weight, the
@@ -1201,9 +1201,42 @@ def flame_combine(xs: Sequence, scales: Sequence[float], weights: Sequence[float
     table = _flame_table("flame_combine", xs, median)
     s = (C.c_double * max(1, c))(*[float(v) for v in scales])
     w = (C.c_double * max(1, c))(*[float(v) if k else float("nan") for v, k in zip(weights, keep)])
-    L.check(L.lib().sa_flame_combine(table, s, w, c, _XTYPE.get(median.dtype, -1), n, _ptr(median), float(divisor),
-                                     _ptr(out), C.c_void_p(_stream(median))), "sa_flame_combine")
+    L.check(getattr(L.lib(), _entry)(table, s, w, c, _XTYPE.get(median.dtype, -1), n, _ptr(median), float(divisor),
+                                     _ptr(out), C.c_void_p(_stream(median))), _entry)
     return out
+
+
+def flame_wide_scratch_bytes(n: int, n_clients: int, dtype: torch.dtype) -> int:
+    """Bytes of device scratch ``flame_stats_wide`` needs for ``n`` elements of ``n_clients`` (17..64) clients."""
+    return _scratch_bytes("flame_wide_scratch_bytes", "sa_flame_wide_scratch_bytes", (n, n_clients), dtype)
+
+
+def flame_stats_wide(xs: Sequence, median_out: torch.Tensor, scratch: torch.Tensor, stats: torch.Tensor, *,
+                     accumulate: bool = False) -> torch.Tensor:
+    """``flame_stats`` for 17 to ``SA_FLAME_WIDE_MAX_CLIENTS`` clients: the same
+    median and the same packed statistics, through ``flame_wide_scratch_bytes``
+    bytes of scratch.  See sa_flame_stats_wide in include/sfl_sa.h."""
+    _require_gpu(median_out, scratch, stats)
+    c, n = len(xs), median_out.numel()
+    if not median_out.is_contiguous() or not stats.is_contiguous() or stats.dtype != torch.float64:
+        raise ValueError("flame_stats_wide: contiguous tensors; stats is float64")
+    xt = _XTYPE.get(median_out.dtype, -1)
+    if L.SA_FLAME_MAX_CLIENTS < c <= L.SA_FLAME_WIDE_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64):
+        if stats.numel() < flame_stat_count(c):
+            raise ValueError("flame_stats_wide: stats smaller than flame_stat_count(len(xs))")
+        _require_scratch("flame_stats_wide", scratch, flame_wide_scratch_bytes(n, c, median_out.dtype),
+                         "flame_wide_scratch_bytes(n, n_clients, dtype)")
+    table = _flame_table("flame_stats_wide", xs, median_out)
+    L.check(L.lib().sa_flame_stats_wide(table, c, xt, n, _ptr(median_out), _ptr(scratch), _ptr(stats),
+                                        int(bool(accumulate)), C.c_void_p(_stream(median_out))), "sa_flame_stats_wide")
+    return stats
+
+
+def flame_combine_wide(xs: Sequence, scales: Sequence[float], weights: Sequence[float], keep: Sequence[bool],
+                       median: torch.Tensor, divisor: float, out: torch.Tensor) -> torch.Tensor:
+    """``flame_combine`` for 17 to ``SA_FLAME_WIDE_MAX_CLIENTS`` clients.  See
+    sa_flame_combine_wide in include/sfl_sa.h."""
+    return flame_combine(xs, scales, weights, keep, median, divisor, out, _entry="sa_flame_combine_wide")
 
 
 # ---------------------------------------------------------------------------

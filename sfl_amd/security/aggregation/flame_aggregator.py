@@ -7,7 +7,8 @@ averaged.
 The definition (``C`` clients in list order, each a list of ``L`` layers of
 one float type ``T``, float32 or float64; ``flame_host`` below is the same
 text as code, and the device path computes the same numbers with
-``sa_flame_stats`` / ``sa_flame_combine``, include/sfl_sa.h):
+``sa_flame_stats`` / ``sa_flame_combine``, or for 17 to 64 clients with
+``sa_flame_stats_wide`` / ``sa_flame_combine_wide``, include/sfl_sa.h):
 
 1. **Median.**  For every layer and element ``g`` = the median of the ``C``
    values in ``T``: the middle one for odd ``C``, ``(lo + hi) / T(2)`` for
@@ -72,6 +73,7 @@ from .aggregator import Aggregator
 
 _FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 MAX_DEVICE_CLIENTS = 16  # SA_FLAME_MAX_CLIENTS: the kernels' client count is a template argument
+WIDE_MAX_DEVICE_CLIENTS = 64  # SA_FLAME_WIDE_MAX_CLIENTS: the client count padded to 32 or 64 in LDS
 
 log = logging.getLogger(__name__)
 
@@ -272,7 +274,10 @@ class FlameAggregator(Aggregator):
     pinned read of the statistics between them, and the result is a list of
     float64 tensors on the device.  Uploads that are all host arrays run the
     numpy form and give float64 arrays.  The device path takes at most 16
-    clients; the host form any number.
+    clients; with ``wide_clients="device"`` rounds of 17 to 64 clients take
+    ``sa_flame_stats_wide`` and ``sa_flame_combine_wide`` on the device too
+    (``last_report["wide_clients"]`` is then true).  The host form takes any
+    number.
 
     After each ``average``, ``last_report`` holds ``labels`` (0 an inlier, -1
     left out), ``norms``, ``threshold``, ``scales`` and ``cosine_distances``.
@@ -285,9 +290,13 @@ class FlameAggregator(Aggregator):
       >>> fl = FLModel(server=server, device_list=clients, model=build, aggregator=aggregator)
     """
 
-    def __init__(self, device: PYU):
+    def __init__(self, device: PYU, wide_clients=None):
         assert isinstance(device, PYU), f"Accepts PYU only but got {type(device)}."
+        if wide_clients not in (None, "device"):
+            raise ValueError(f'wide_clients is None (more than {MAX_DEVICE_CLIENTS} device clients are refused) or '
+                             f'"device", not {wide_clients!r}')
         self.device = device
+        self.wide_clients = wide_clients
         self.last_report = None
 
     # ------------------------------------------------------------ the paths
@@ -296,9 +305,16 @@ class FlameAggregator(Aggregator):
         from ... import kernels as K
 
         C = len(layers[0])
-        if C > MAX_DEVICE_CLIENTS:
+        wide = C > MAX_DEVICE_CLIENTS and self.wide_clients == "device"
+        if wide and C > WIDE_MAX_DEVICE_CLIENTS:
+            raise NotImplementedError(f"FlameAggregator takes at most {WIDE_MAX_DEVICE_CLIENTS} clients on the device "
+                                      f"(SA_FLAME_WIDE_MAX_CLIENTS), got {C}; the host form takes any number")
+        if C > MAX_DEVICE_CLIENTS and not wide:
             raise NotImplementedError(f"FlameAggregator takes at most {MAX_DEVICE_CLIENTS} clients on the device "
                                       f"(SA_FLAME_MAX_CLIENTS), got {C}; the host form takes any number")
+        scratch_bytes, stats_pass, combine_pass = \
+            (K.flame_wide_scratch_bytes, K.flame_stats_wide, K.flame_combine_wide) if wide else \
+            (K.flame_scratch_bytes, K.flame_stats, K.flame_combine)
         on_dev = []
         for l, xs in enumerate(layers):
             row = []
@@ -311,12 +327,12 @@ class FlameAggregator(Aggregator):
                     row.append(H.h2d(x, dev).reshape(-1))
             on_dev.append(row)
         stats = torch.zeros(K.flame_stat_count(C), dtype=torch.float64, device=dev)
-        need = max(K.flame_scratch_bytes(r[0].numel(), C, r[0].dtype) for r in on_dev)
+        need = max(scratch_bytes(r[0].numel(), C, r[0].dtype) for r in on_dev)
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
         medians = []
         for l, row in enumerate(on_dev):
             g = torch.empty_like(row[0])
-            K.flame_stats(row, g, scratch, stats, accumulate=l > 0)
+            stats_pass(row, g, scratch, stats, accumulate=l > 0)
             medians.append(g)
         report = decide(H.d2h(stats, pooled=False), C)  # the one read between the two passes
         keep = [lb == 0 for lb in report["labels"]]
@@ -331,8 +347,10 @@ class FlameAggregator(Aggregator):
                 outs.append(H.h2d(host, dev).reshape(tuple(xs[0].shape)))
                 continue
             out = torch.empty(g.numel(), dtype=torch.float64, device=dev)
-            K.flame_combine(row, report["scales"], w, keep, g, W, out)
+            combine_pass(row, report["scales"], w, keep, g, W, out)
             outs.append(out.reshape(tuple(xs[0].shape)))
+        if wide:
+            report["wide_clients"] = True
         self.last_report = report
         return outs
 

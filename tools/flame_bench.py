@@ -28,7 +28,15 @@ timed with device events.  One JSON line per case:
   same: the median has torch's bits, the statistics agree to 1e-9 relatively,
     the combine to 1e-12.
 
+--wide measures sa_flame_stats_wide / sa_flame_combine_wide
+(sfl_amd/csrc/sa_flame_wide.hip) instead: float32 at C = 32 and C = 64,
+float64 at C = 32, against the same torch chain.  One pass over the clients
+(stats C n s + n s); the Gram products' model is the padded client count's
+upper-triangle 16 x 16 tiles, 512 float64 FMAs each per 4 elements, reported as
+TFLOP/s and as a fraction of FP64_MATRIX_PEAK_TFLOPS.
+
 usage: python tools/flame_bench.py [--elems 100000000] [--reps 5] [--torch-reps 2] [--passes 3] [--out FILE]
+       python tools/flame_bench.py --wide [--out profiles/flame/flame_wide_bench.jsonl]
 """
 import argparse
 import json
@@ -38,6 +46,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+FP64_MATRIX_PEAK_TFLOPS = 78.6  # the MI355X data sheet's float64 matrix rate
 
 
 def main():
@@ -47,8 +56,11 @@ def main():
     ap.add_argument("--torch-reps", type=int, default=2)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--torch-chunks", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flame", "flame_bench.jsonl"))
+    ap.add_argument("--wide", action="store_true", help="the 17..64-client entries at C = 32 and 64")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "flame",
+                                        "flame_wide_bench.jsonl" if args.wide else "flame_bench.jsonl")
     import torch
 
     from benchkit.roofline import HBM_PEAK_GBPS
@@ -95,14 +107,19 @@ def main():
         lines.append(line)
         print(json.dumps(line), flush=True)
 
-    for tdt, C in ((torch.float32, 8), (torch.float32, 16), (torch.float64, 8)):
+    narrow = ((torch.float32, 8), (torch.float32, 16), (torch.float64, 8))
+    wide = ((torch.float32, 32), (torch.float32, 64), (torch.float64, 32))
+    scratch_bytes, stats_pass, combine_pass = \
+        (K.flame_wide_scratch_bytes, K.flame_stats_wide, K.flame_combine_wide) if args.wide else \
+        (K.flame_scratch_bytes, K.flame_stats, K.flame_combine)
+    for tdt, C in wide if args.wide else narrow:
         g = torch.Generator(device=dev).manual_seed(11)
         xs = [torch.randn(n, generator=g, device=dev, dtype=tdt) for _ in range(C)]
         s = xs[0].element_size()
         name = str(tdt).replace("torch.", "")
         S = K.flame_stat_count(C)
         median = torch.empty(n, dtype=tdt, device=dev)
-        scratch = torch.empty(K.flame_scratch_bytes(n, C, tdt), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(scratch_bytes(n, C, tdt), dtype=torch.uint8, device=dev)
         stats = torch.zeros(S, dtype=torch.float64, device=dev)
         out = torch.empty(n, dtype=torch.float64, device=dev)
         # fixed decisions: every second client clipped, the last one left out
@@ -115,7 +132,7 @@ def main():
         keepers = {}
 
         def hip_stats():
-            K.flame_stats(xs, median, scratch, stats)
+            stats_pass(xs, median, scratch, stats)
 
         def torch_stats():
             gram = torch.zeros((C, C), dtype=torch.float64, device=dev)
@@ -132,7 +149,7 @@ def main():
             keepers["t"] = (meds, gram, norms)
 
         def hip_combine():
-            K.flame_combine(xs, scales, weights, keep, median, W, out)
+            combine_pass(xs, scales, weights, keep, median, W, out)
 
         def torch_combine():
             outs = []
@@ -151,7 +168,7 @@ def main():
         def torch_both():
             torch_stats(), torch_combine()
 
-        passes = 1 if C <= 8 else 2
+        passes = 1 if C <= 8 or args.wide else 2
         second = 0
         if passes == 2:  # the second pass reads the clients of its rows only (sa_flame.hip first_rows)
             r, have = 0, 0
@@ -168,8 +185,14 @@ def main():
         want = torch.cat([gram[iu[0], iu[1]], norms])
         same_median = bool(torch.equal(torch.cat(meds).view(torch.uint8), median.view(torch.uint8)))
         same = same_median and bool(torch.allclose(stats, want, rtol=1e-9, atol=0))
+        extra = {}
+        if args.wide:  # the Gram products as the matrix unit runs them: the padded count's triangle tiles
+            tiles = (2 if C <= 32 else 4) * ((2 if C <= 32 else 4) + 1) // 2
+            tflops = 2 * tiles * 512 * (n / 4) / (hip_ms * 1e-3) / 1e12
+            extra = {"gram_tiles": tiles, "gram_matrix_tflops": round(tflops, 2),
+                     "gram_frac_fp64_matrix_peak": round(tflops / FP64_MATRIX_PEAK_TFLOPS, 4)}
         emit("stats", name, C, hip_ms, torch_ms, hs, ts, stats_model, same, launches=passes + 1, passes_over_x=passes,
-             fma_model=fmas, gfma_per_s=round(fmas / (hip_ms * 1e-3) / 1e9, 1), same_median=same_median)
+             fma_model=fmas, gfma_per_s=round(fmas / (hip_ms * 1e-3) / 1e9, 1), same_median=same_median, **extra)
 
         hip_ms, torch_ms, hs, ts = ab(hip_combine, torch_combine)
         same = bool(torch.allclose(out, torch.cat(keepers["c"]), rtol=1e-12, atol=0))
