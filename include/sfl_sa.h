@@ -1184,6 +1184,79 @@ int sa_flame_stats_wide(const void* const* x, int n_clients, int x_type, uint64_
 int sa_flame_combine_wide(const void* const* x, const double* scale, const double* weight, int n_clients, int x_type,
                           uint64_t n, const void* median, double divisor, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* PPBAggregator: batched Paillier aggregation (the reference's         */
+/* phe_paillier_batch_aggregator, sfl/security/aggregation/experiment/  */
+/* ppb_aggregator.py:249-420).  sfl_amd/security/aggregation/           */
+/* ppb_aggregator.py has the definition and the host form in Python     */
+/* integers.  key_bits K is the size of n: 128, 256, 512, 1024 or 2048; */
+/* any other positive K is refused with SA_ERR_UNSUPPORTED (the class   */
+/* then takes the host form).  Numbers are little-endian uint32 limbs   */
+/* in ordinary (not Montgomery) form, rows contiguous: a plaintext row  */
+/* has LN = K / 32 limbs, a ciphertext row 2 LN.                        */
+/* consts: the key's constants, sa_ppb_consts_words(K) = 8 + 11 LN      */
+/* words on the device, written by the host: [0] K, [1] -(n^2)^-1 mod   */
+/* 2^32, [2] -n^-1 mod 2^32, [3] the bit length of lambda, [4..7] 0,    */
+/* then n^2, R^2 mod n^2, R mod n^2, n R mod n^2 (2 LN limbs each, R =  */
+/* 2^(2 K)), n, lambda = lcm(p - 1, q - 1), mu R' mod n (LN limbs each, */
+/* R' = 2^K, mu = ((g^lambda mod n^2 - 1) / n)^-1 mod n with g = n + 1).*/
+/* An encrypting party needs n only: its lambda and mu R' are zeros.    */
+/*   sa_ppb_encode   n elements of x_type (SA_F32, SA_F64, SA_I64) to   */
+/*           ceil(n / per_row) plaintext rows, per_row = K / field_bits */
+/*           fields of field_bits bits a row, the row's first element   */
+/*           the most significant of the cnt <= per_row fields it       */
+/*           holds.  field = trunc(|x w / total + bias| expand), every  */
+/*           step a rounded float64 operation in this order (:74-75 and */
+/*           :105).  x w / total + bias NaN, negative, or a field above */
+/*           (2^field_bits - 1) / n_parties (the parties' sum must not  */
+/*           carry into the next field) set SA_PPB_FLAG_NAN, _NEGATIVE, */
+/*           _RANGE in *flags (|=) and store a zero field.  field_bits  */
+/*           in 32..63; others SA_ERR_UNSUPPORTED.                      */
+/*   sa_ppb_encrypt  ct[j] = (1 + m_j n) r_j^n mod n^2.  r_j is the     */
+/*           first candidate t < 64 with 0 < r < n, candidate t the     */
+/*           first LN words (little-endian limbs) of the ChaCha20       */
+/*           keystream (sa_chacha20_keystream's block function) of      */
+/*           (key, nonce) from block (64 j + t) ceil(K / 512); none     */
+/*           (probability below 2^-64): SA_PPB_FLAG_NO_R.  m_j < n.     */
+/*   sa_ppb_add      out[j] = prod_p cts[p][j] mod n^2; cts is a HOST   */
+/*           table of 1..SA_PPB_MAX_PARTIES device pointers and reaches */
+/*           the kernel by value; every input is below n^2.             */
+/*   sa_ppb_decrypt  plain[j] = ((ct[j]^lambda mod n^2 - 1) / n) mu mod */
+/*           n; scratch: rows 2 LN words, overwritten.                  */
+/*   sa_ppb_decode   out[e] = field / expand - n_parties bias in        */
+/*           float64 (:219-221): a correctly rounded conversion, the    */
+/*           IEEE division, the subtraction.                            */
+/* rows == 0 and n == 0 return SA_OK after the checks of the scalars.   */
+/* rows >= 2^30, n >= 2^40, a consts size other than sa_ppb_consts_     */
+/* words, null and misaligned pointers are refused before any launch.   */
+/* Everything is stream-ordered, allocates nothing and never            */
+/* synchronises with the host; the same input gives the same bits.      */
+/* Not constant-time against a co-tenant of the device.  ABI version 3  */
+/* (additive).                                                          */
+/* ------------------------------------------------------------------ */
+#define SA_PPB_MAX_PARTIES 64
+#define SA_PPB_FLAG_NEGATIVE 1u
+#define SA_PPB_FLAG_NAN 2u
+#define SA_PPB_FLAG_RANGE 4u
+#define SA_PPB_FLAG_NO_R 8u
+
+int sa_ppb_consts_words(int key_bits);
+
+int sa_ppb_encode(const void* x, int x_type, uint64_t n, double w, double total, int n_parties, double bias,
+                  double expand, int key_bits, int field_bits, uint32_t* plain_out, uint32_t* flags, void* stream);
+
+int sa_ppb_encrypt(const uint32_t* plain, uint64_t rows, int key_bits, const uint32_t* consts, uint64_t n_consts,
+                   const uint32_t key[8], uint64_t nonce, uint32_t* ct_out, uint32_t* flags, void* stream);
+
+int sa_ppb_add(const uint32_t* const* cts, int n_parties, uint64_t rows, int key_bits, const uint32_t* consts,
+               uint64_t n_consts, uint32_t* out, void* stream);
+
+int sa_ppb_decrypt(const uint32_t* ct, uint64_t rows, int key_bits, const uint32_t* consts, uint64_t n_consts,
+                   uint32_t* scratch, uint32_t* plain_out, void* stream);
+
+int sa_ppb_decode(const uint32_t* plain, uint64_t n, int n_parties, double bias, double expand, int key_bits,
+                  int field_bits, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

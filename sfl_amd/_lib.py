@@ -33,6 +33,9 @@ SA_FLAME_MAX_CLIENTS = 16
 SA_FLAME_WIDE_MAX_CLIENTS = 64
 SA_MARS_MAX_P = 32
 SA_MARS_WIDE_MAX_P = 512
+SA_PPB_MAX_PARTIES = 64
+SA_PPB_FLAG_NEGATIVE, SA_PPB_FLAG_NAN, SA_PPB_FLAG_RANGE, SA_PPB_FLAG_NO_R = 1, 2, 4, 8
+SA_PPB_KEY_BITS = (128, 256, 512, 1024, 2048)
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -58,6 +61,7 @@ EXPORTED = (
     "sa_smp_mask_host", "sa_smp_mask", "sa_smp_delta_f32", "sa_smp_sumsq_f32", "sa_smp_perturb_f32",
     "sa_smp_finish_f32",
     "sa_mask_pack2", "sa_fused_clients_pack2", "sa_decode_pack2",
+    "sa_ppb_consts_words", "sa_ppb_encode", "sa_ppb_encrypt", "sa_ppb_add", "sa_ppb_decrypt", "sa_ppb_decode",
 )
 
 
@@ -201,6 +205,12 @@ def _declare(lib):
     lib.sa_freq_scratch_bytes.argtypes = [u64, u64, i32, i32]
     lib.sa_freq_features.argtypes = [P(C.c_void_p), i32, i32, u64, u64, vp, vp, vp]
     lib.sa_freq_gram.argtypes = [vp, i32, u64, vp, vp]
+    lib.sa_ppb_consts_words.argtypes = [i32]
+    lib.sa_ppb_encode.argtypes = [vp, i32, u64, dbl, dbl, i32, dbl, dbl, i32, i32, vp, vp, vp]
+    lib.sa_ppb_encrypt.argtypes = [vp, u64, i32, vp, u64, P(C.c_uint32), u64, vp, vp, vp]
+    lib.sa_ppb_add.argtypes = [P(C.c_void_p), i32, u64, i32, vp, u64, vp, vp]
+    lib.sa_ppb_decrypt.argtypes = [vp, u64, i32, vp, u64, vp, vp, vp]
+    lib.sa_ppb_decode.argtypes = [vp, u64, i32, dbl, dbl, i32, i32, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -1392,3 +1392,107 @@ def freq_gram(feats: torch.Tensor, n_clients: int, length: int, out: torch.Tenso
     L.check(L.lib().sa_freq_gram(_ptr(feats), int(n_clients), int(length), _ptr(out), C.c_void_p(_stream(feats))),
             "sa_freq_gram")
     return out
+
+
+# ---------------------------------------------------------------------------
+# PPBAggregator (sa_ppb_*; security/aggregation/ppb_aggregator.py on top)
+# ---------------------------------------------------------------------------
+LIMB = torch.int32  # storage dtype for uint32 limb buffers
+
+
+def ppb_consts_words(key_bits: int) -> int:
+    """Words of the key's constants buffer; a key size the kernels do not take
+    raises ``SALibraryError`` with code ``SA_ERR_UNSUPPORTED``."""
+    rc = L.lib().sa_ppb_consts_words(int(key_bits))
+    if rc < 0:
+        L.check(rc, "sa_ppb_consts_words")
+    return rc
+
+
+def _ppb_limbs(what: str, name: str, t: torch.Tensor, words: int, like: torch.Tensor | None = None) -> None:
+    _require_gpu(t)
+    if t.dtype != LIMB or not t.is_contiguous() or t.numel() < words or (like is not None and t.device != like.device):
+        raise ValueError(f"{what}: {name} is contiguous int32 (uint32 limbs) with {words} words, on one device")
+
+
+def _ppb_fields(key_bits: int, field_bits: int, n: int) -> int:
+    """Plaintext words of ``n`` elements."""
+    per_row = max(1, key_bits // max(1, field_bits))
+    return -(-n // per_row) * (key_bits // 32)
+
+
+def ppb_encode(x: torch.Tensor, w: float, total: float, n_parties: int, bias: float, expand: float, key_bits: int,
+               field_bits: int, plain_out: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """``x`` (float32, float64 or int64) to plaintext rows of ``key_bits / 32``
+    limbs in ``plain_out``; refusals are or-ed into ``flags`` (one int32
+    word).  See sa_ppb_encode in include/sfl_sa.h."""
+    _require_gpu(x)
+    if not x.is_contiguous():
+        raise ValueError("ppb_encode: x is contiguous")
+    _ppb_limbs("ppb_encode", "plain_out", plain_out, _ppb_fields(key_bits, field_bits, x.numel()), x)
+    _ppb_limbs("ppb_encode", "flags", flags, 1, x)
+    L.check(L.lib().sa_ppb_encode(_ptr(x), _XTYPE.get(x.dtype, -1), x.numel(), float(w), float(total), int(n_parties),
+                                  float(bias), float(expand), int(key_bits), int(field_bits), _ptr(plain_out),
+                                  _ptr(flags), C.c_void_p(_stream(x))), "sa_ppb_encode")
+    return plain_out
+
+
+def ppb_decode(plain: torch.Tensor, n_parties: int, bias: float, expand: float, key_bits: int, field_bits: int,
+               out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float64, its element count the fields') from plaintext rows.  See sa_ppb_decode."""
+    _require_gpu(out)
+    if out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("ppb_decode: out is contiguous float64")
+    _ppb_limbs("ppb_decode", "plain", plain, _ppb_fields(key_bits, field_bits, out.numel()), out)
+    L.check(L.lib().sa_ppb_decode(_ptr(plain), out.numel(), int(n_parties), float(bias), float(expand), int(key_bits),
+                                  int(field_bits), _ptr(out), C.c_void_p(_stream(out))), "sa_ppb_decode")
+    return out
+
+
+def _ppb_consts(what: str, consts: torch.Tensor, key_bits: int) -> int:
+    words = ppb_consts_words(key_bits)
+    _require_gpu(consts)
+    if consts.dtype != LIMB or not consts.is_contiguous() or consts.numel() != words:
+        raise ValueError(f"{what}: consts is contiguous int32 with {words} words")
+    return words
+
+
+def ppb_encrypt(plain: torch.Tensor, rows: int, key_bits: int, consts: torch.Tensor, key: bytes, nonce: int,
+                ct_out: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """``ct_out`` (``rows`` of ``key_bits / 16`` limbs) = the Paillier
+    encryptions of ``plain``'s rows under the ChaCha20 ``(key, nonce)``.  See sa_ppb_encrypt."""
+    words = _ppb_consts("ppb_encrypt", consts, key_bits)
+    _ppb_limbs("ppb_encrypt", "plain", plain, rows * (key_bits // 32), consts)
+    _ppb_limbs("ppb_encrypt", "ct_out", ct_out, rows * (key_bits // 16), consts)
+    _ppb_limbs("ppb_encrypt", "flags", flags, 1, consts)
+    L.check(L.lib().sa_ppb_encrypt(_ptr(plain), int(rows), int(key_bits), _ptr(consts), words, L.chacha_key_words(key),
+                                   int(nonce) & ((1 << 64) - 1), _ptr(ct_out), _ptr(flags),
+                                   C.c_void_p(_stream(consts))), "sa_ppb_encrypt")
+    return ct_out
+
+
+def ppb_add(cts: Sequence[torch.Tensor], rows: int, key_bits: int, consts: torch.Tensor,
+            out: torch.Tensor) -> torch.Tensor:
+    """``out`` = the row-wise product mod n^2 of the parties' ciphertext arrays.  See sa_ppb_add."""
+    words = _ppb_consts("ppb_add", consts, key_bits)
+    table = (C.c_void_p * max(1, len(cts)))()
+    for i, ct in enumerate(cts):
+        _ppb_limbs("ppb_add", f"party {i}'s ciphertexts", ct, rows * (key_bits // 16), consts)
+        table[i] = ct.data_ptr()
+    _ppb_limbs("ppb_add", "out", out, rows * (key_bits // 16), consts)
+    L.check(L.lib().sa_ppb_add(table, len(cts), int(rows), int(key_bits), _ptr(consts), words, _ptr(out),
+                               C.c_void_p(_stream(consts))), "sa_ppb_add")
+    return out
+
+
+def ppb_decrypt(ct: torch.Tensor, rows: int, key_bits: int, consts: torch.Tensor, scratch: torch.Tensor,
+                plain_out: torch.Tensor) -> torch.Tensor:
+    """``plain_out`` (``rows`` of ``key_bits / 32`` limbs) = the decryptions of
+    ``ct``'s rows; ``scratch``: as many words as ``ct``, overwritten.  See sa_ppb_decrypt."""
+    words = _ppb_consts("ppb_decrypt", consts, key_bits)
+    _ppb_limbs("ppb_decrypt", "ct", ct, rows * (key_bits // 16), consts)
+    _ppb_limbs("ppb_decrypt", "scratch", scratch, rows * (key_bits // 16), consts)
+    _ppb_limbs("ppb_decrypt", "plain_out", plain_out, rows * (key_bits // 32), consts)
+    L.check(L.lib().sa_ppb_decrypt(_ptr(ct), int(rows), int(key_bits), _ptr(consts), words, _ptr(scratch),
+                                   _ptr(plain_out), C.c_void_p(_stream(consts))), "sa_ppb_decrypt")
+    return plain_out

@@ -7,3 +7,4 @@ from .sparse_plain_aggregator import SparsePlainAggregator  # noqa: F401
 from .flame_aggregator import FlameAggregator  # noqa: F401
 from .mars_aggregator import MarsAggregator  # noqa: F401
 from .freq_aggregator import FreqAggregator  # noqa: F401
+from .ppb_aggregator import PPBAggregator  # noqa: F401
