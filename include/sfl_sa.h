@@ -1257,6 +1257,73 @@ int sa_ppb_decrypt(const uint32_t* ct, uint64_t rows, int key_bits, const uint32
 int sa_ppb_decode(const uint32_t* plain, uint64_t n, int n_parties, double bias, double expand, int key_bits,
                   int field_bits, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* FeatureHistogram: the node histograms of the reference's homo_boost  */
+/* (sfl/ml/boost/homo_boost/tree_core/feature_histogram.py:99-287) for  */
+/* one party's rows x F data on one device.  sfl_amd/ml/boost/          */
+/* feature_histogram.py has the definition and the host form in numpy.  */
+/* bmax: the largest number of split points of any feature, 0 ..        */
+/* SA_HIST_MAX_BINS.                                                    */
+/*   sa_hist_codes   codes_out[r F + f] = the number of feature f's     */
+/*           split points <= x[r F + f], compared in float64; NaN gives */
+/*           the feature's count nb_f ("beyond").  The reference's      */
+/*           bucket b, x < split[b] (:204-212), is code <= b.  x: x_type*/
+/*           (SA_F32 or SA_F64), row-major.  splits: the features'      */
+/*           ascending split points back to back in float64 on the      */
+/*           device, feature f's at [offsets[f], offsets[f + 1]);       */
+/*           offsets: F + 1 int32 on the device.  A block stages its    */
+/*           eight features' tables in LDS and searches them without    */
+/*           branches in at most 8 probes.                              */
+/*   sa_hist_build   the integer image of a batch of n_nodes slots in   */
+/*           scratch (:246-262 and :275-279, the loops over features,   */
+/*           split points and rows): for every (slot, feature, code)    */
+/*           the sums of q_grad, q_hess and 1 over the rows r with      */
+/*           node_of_row[r] == slot and that code, q = int64(rint(v     */
+/*           2^k)) with k_grad, k_hess from the host (no sum of q may   */
+/*           reach 2^63: the caller's rule).  node_of_row: int32, a     */
+/*           value outside 0 .. n_nodes - 1 is a row of no node.  grad  */
+/*           and hess: g_type (SA_F32 or SA_F64).  Integer atomics in   */
+/*           LDS and in global memory only: the image is the same       */
+/*           whatever the schedule.  The image is cleared first; what   */
+/*           scratch held before does not matter.  sa_hist_geometry     */
+/*           states how the batch is launched: out4 = (features per     */
+/*           block, slots per launch, launches, bytes of LDS of a       */
+/*           block).  A code above bmax is never used as an index.      */
+/*   sa_hist_finish  out[((slot F + f) B + b) 3 + (0, 1, 2)] = (G 2^    */
+/*           -k_grad, H 2^-k_hess, N) in float64, G, H, N the image's   */
+/*           sums over code <= b, for b < n_bins[f]; B = bmax +         */
+/*           (use_missing ? 1 : 0).  With use_missing bucket n_bins[f]  */
+/*           is the slot's totals over all codes less bucket n_bins[f]  */
+/*           - 1 (:280-284).  Every other entry, and a feature with     */
+/*           n_bins[f] < 0 (not valid, :285-286), is +0.0 (:165-193).   */
+/*           n_bins: F int32 on the device.  One wave a (slot, feature).*/
+/* scratch: sa_hist_scratch_bytes = n_nodes F (bmax + 1) 20 bytes,      */
+/* rounded up to 8, 8-byte aligned; a size above 2^31 - 1 is refused    */
+/* with SA_ERR_UNSUPPORTED.  Calls with no rows, features or nodes      */
+/* return SA_OK after the checks of the scalars and look at no pointer  */
+/* (sa_hist_build without rows still clears the image).  Other element  */
+/* types, bmax outside 0 .. SA_HIST_MAX_BINS, rows >= 2^31, n_nodes >=  */
+/* 2^24, F >= 2^16, a scale outside -2100 .. 2100, null and misaligned  */
+/* pointers are refused before any launch.  Everything is stream-       */
+/* ordered, allocates nothing and never synchronises with the host.     */
+/* ABI version 3 (additive).                                            */
+/* ------------------------------------------------------------------ */
+#define SA_HIST_MAX_BINS 255
+
+int sa_hist_scratch_bytes(uint64_t n_nodes, uint64_t n_features, int bmax);
+
+int sa_hist_geometry(int bmax, int n_nodes, uint64_t n_features, int* out4);
+
+int sa_hist_codes(const void* x, int x_type, uint64_t rows, uint64_t n_features, const double* splits,
+                  const int32_t* offsets, int bmax, uint8_t* codes_out, void* stream);
+
+int sa_hist_build(const uint8_t* codes, uint64_t rows, uint64_t n_features, int bmax, const int32_t* node_of_row,
+                  int n_nodes, const void* grad, const void* hess, int g_type, int k_grad, int k_hess, void* scratch,
+                  void* stream);
+
+int sa_hist_finish(const void* scratch, int n_nodes, uint64_t n_features, int bmax, const int32_t* n_bins, int k_grad,
+                   int k_hess, int use_missing, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ SA_MARS_WIDE_MAX_P = 512
 SA_PPB_MAX_PARTIES = 64
 SA_PPB_FLAG_NEGATIVE, SA_PPB_FLAG_NAN, SA_PPB_FLAG_RANGE, SA_PPB_FLAG_NO_R = 1, 2, 4, 8
 SA_PPB_KEY_BITS = (128, 256, 512, 1024, 2048)
+SA_HIST_MAX_BINS = 255
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -62,6 +63,7 @@ EXPORTED = (
     "sa_smp_finish_f32",
     "sa_mask_pack2", "sa_fused_clients_pack2", "sa_decode_pack2",
     "sa_ppb_consts_words", "sa_ppb_encode", "sa_ppb_encrypt", "sa_ppb_add", "sa_ppb_decrypt", "sa_ppb_decode",
+    "sa_hist_scratch_bytes", "sa_hist_geometry", "sa_hist_codes", "sa_hist_build", "sa_hist_finish",
 )
 
 
@@ -211,6 +213,11 @@ def _declare(lib):
     lib.sa_ppb_add.argtypes = [P(C.c_void_p), i32, u64, i32, vp, u64, vp, vp]
     lib.sa_ppb_decrypt.argtypes = [vp, u64, i32, vp, u64, vp, vp, vp]
     lib.sa_ppb_decode.argtypes = [vp, u64, i32, dbl, dbl, i32, i32, vp, vp]
+    lib.sa_hist_scratch_bytes.argtypes = [u64, u64, i32]
+    lib.sa_hist_geometry.argtypes = [i32, i32, u64, P(C.c_int)]
+    lib.sa_hist_codes.argtypes = [vp, i32, u64, u64, vp, vp, i32, vp, vp]
+    lib.sa_hist_build.argtypes = [vp, u64, u64, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]
+    lib.sa_hist_finish.argtypes = [vp, i32, u64, i32, vp, i32, i32, i32, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -1496,3 +1496,83 @@ def ppb_decrypt(ct: torch.Tensor, rows: int, key_bits: int, consts: torch.Tensor
     L.check(L.lib().sa_ppb_decrypt(_ptr(ct), int(rows), int(key_bits), _ptr(consts), words, _ptr(scratch),
                                    _ptr(plain_out), C.c_void_p(_stream(consts))), "sa_ppb_decrypt")
     return plain_out
+
+
+# ---------------------------------------------------------------------------
+# FeatureHistogram (sa_hist_*; ml/boost/feature_histogram.py on top)
+# ---------------------------------------------------------------------------
+def hist_scratch_bytes(n_nodes: int, n_features: int, bmax: int) -> int:
+    """Bytes of device scratch (the integer image) of a batch of ``n_nodes``
+    slots, ``n_features`` features and ``bmax`` split points at most; a size the
+    library does not take raises ``SALibraryError`` with ``SA_ERR_UNSUPPORTED``."""
+    rc = L.lib().sa_hist_scratch_bytes(int(n_nodes), int(n_features), int(bmax))
+    if rc < 0:
+        L.check(rc, "sa_hist_scratch_bytes")
+    return rc
+
+
+def hist_geometry(bmax: int, n_nodes: int, n_features: int) -> tuple:
+    """``(features per block, slots per launch, launches, LDS bytes of a block)``
+    of ``hist_build`` for such a batch; needs no GPU."""
+    out = (C.c_int * 4)()
+    L.check(L.lib().sa_hist_geometry(int(bmax), int(n_nodes), int(n_features), out), "sa_hist_geometry")
+    return tuple(out)
+
+
+def _hist_vec(what: str, name: str, t: torch.Tensor, dtype, numel: int, like: torch.Tensor) -> None:
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel or t.device != like.device:
+        raise ValueError(f"{what}: {name} is contiguous {dtype} with at least {numel} elements on the data's device")
+
+
+def hist_codes(x: torch.Tensor, splits: torch.Tensor, offsets: torch.Tensor, bmax: int,
+               codes_out: torch.Tensor) -> torch.Tensor:
+    """``codes_out`` (uint8, ``rows x F``) = for every element of the
+    ``rows x F`` tensor ``x`` the number of its feature's split points that are
+    ``<= x``.  See sa_hist_codes in include/sfl_sa.h."""
+    _require_gpu(x, splits, offsets, codes_out)
+    xt = _float_xtype("hist_codes", x.dtype)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("hist_codes: x is a contiguous rows x features tensor")
+    rows, nf = x.shape
+    _hist_vec("hist_codes", "offsets", offsets, torch.int32, nf + 1, x)
+    _hist_vec("hist_codes", "splits", splits, torch.float64, 0, x)
+    _hist_vec("hist_codes", "codes_out", codes_out, torch.uint8, rows * nf, x)
+    L.check(L.lib().sa_hist_codes(_ptr(x), xt, rows, nf, _ptr(splits), _ptr(offsets), int(bmax), _ptr(codes_out),
+                                  C.c_void_p(_stream(x))), "sa_hist_codes")
+    return codes_out
+
+
+def hist_build(codes: torch.Tensor, bmax: int, node_of_row: torch.Tensor, n_nodes: int, grad: torch.Tensor,
+               hess: torch.Tensor, k_grad: int, k_hess: int, scratch: torch.Tensor) -> torch.Tensor:
+    """The integer image of the batch's ``n_nodes`` histograms into
+    ``scratch``.  See sa_hist_build in include/sfl_sa.h."""
+    _require_gpu(codes, node_of_row, grad, hess, scratch)
+    gt = _float_xtype("hist_build", grad.dtype)
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise ValueError("hist_build: the codes are a contiguous rows x features uint8 tensor")
+    rows, nf = codes.shape
+    _hist_vec("hist_build", "node_of_row", node_of_row, torch.int32, rows, codes)
+    _hist_vec("hist_build", "grad", grad, grad.dtype, rows, codes)
+    _hist_vec("hist_build", "hess", hess, grad.dtype, rows, codes)
+    _require_scratch("hist_build", scratch, hist_scratch_bytes(n_nodes, nf, bmax),
+                     "hist_scratch_bytes(n_nodes, n_features, bmax)")
+    L.check(L.lib().sa_hist_build(_ptr(codes), rows, nf, int(bmax), _ptr(node_of_row), int(n_nodes), _ptr(grad),
+                                  _ptr(hess), gt, int(k_grad), int(k_hess), _ptr(scratch),
+                                  C.c_void_p(_stream(codes))), "sa_hist_build")
+    return scratch
+
+
+def hist_finish(scratch: torch.Tensor, n_nodes: int, n_features: int, bmax: int, n_bins: torch.Tensor, k_grad: int,
+                k_hess: int, use_missing: bool, out: torch.Tensor) -> torch.Tensor:
+    """``out`` (float64, ``n_nodes x F x (bmax [+ 1]) x 3``) = the cumulative
+    ``(G, H, N)`` triples of the image in ``scratch``.  See sa_hist_finish."""
+    _require_gpu(scratch, n_bins, out)
+    buckets = int(bmax) + (1 if use_missing else 0)
+    _hist_vec("hist_finish", "n_bins", n_bins, torch.int32, n_features, scratch)
+    _hist_vec("hist_finish", "out", out, torch.float64, n_nodes * n_features * buckets * 3, scratch)
+    _require_scratch("hist_finish", scratch, hist_scratch_bytes(n_nodes, n_features, bmax),
+                     "hist_scratch_bytes(n_nodes, n_features, bmax)")
+    L.check(L.lib().sa_hist_finish(_ptr(scratch), int(n_nodes), int(n_features), int(bmax), _ptr(n_bins), int(k_grad),
+                                   int(k_hess), 1 if use_missing else 0, _ptr(out), C.c_void_p(_stream(scratch))),
+            "sa_hist_finish")
+    return out

@@ -1,0 +1,3 @@
+from .boost import FeatureHistogram
+
+__all__ = ["FeatureHistogram"]
