@@ -1324,6 +1324,61 @@ int sa_hist_build(const uint8_t* codes, uint64_t rows, uint64_t n_features, int 
 int sa_hist_finish(const void* scratch, int n_nodes, uint64_t n_features, int bmax, const int32_t* n_bins, int k_grad,
                    int k_hess, int use_missing, double* out, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* HomoBinning: one party's local quantities for the reference's        */
+/* federated quantile binning (sfl/preprocessing/binning/               */
+/* homo_binning.py:106-151, homo_binning_base.py:150-159 and :208-247)  */
+/* from its rows x F data on one device.  sfl_amd/preprocessing/        */
+/* binning/homo_binning.py has the definition and the host form.  x:    */
+/* x_type (SA_F32 or SA_F64), row-major.  A value is valid if it is not */
+/* NaN and equals none of the n_abnormal <= SA_BIN_MAX_ABNORMAL values  */
+/* of abnormal (a host array, read by the call and passed by value;     */
+/* compared after conversion to x_type).                                */
+/*   sa_bin_range  out[4 f + (0, 1, 2, 3)] = min, max (float64 bits),   */
+/*           count of valid values and count of NaN (int64) of feature  */
+/*           f: what HDataFrame.min / max / count and the summaries'    */
+/*           missing_count give (homo_binning.py:106-115, :141).  A     */
+/*           zero extremum is +0.0; a feature without a valid value has */
+/*           +inf, -inf, 0.  Ordered integer keys and integer atomics:  */
+/*           no order of the rows changes a bit.  out: 4 F 64-bit words */
+/*           on the device, overwritten.                                */
+/*   sa_bin_ranks  ranks_out[f q + j] = the number of valid x[r F + f]  */
+/*           < queries[f q + j], strictly and exactly (float32 data     */
+/*           against the smallest float32 >= the query), int64: the     */
+/*           exact form of QuantileSummaries.batch_query_value under    */
+/*           query_table (homo_binning_base.py:226-247).  queries: F x  */
+/*           q float64 on the device, ascending per feature, q in 1 ..  */
+/*           SA_BIN_MAX_Q; unsorted queries give unspecified counts and */
+/*           no access out of bounds.  ranks_out is cleared by a kernel */
+/*           first: what it held does not matter.  q <=                 */
+/*           SA_BIN_REG_MAX_Q: query points and 32-bit counters in the  */
+/*           lanes' registers; above: tables and counters in LDS, a     */
+/*           binary search and one LDS add an element.                  */
+/*   sa_bin_geometry  how sa_bin_ranks launches: out5 = (form: 0        */
+/*           registers, 1 LDS; query points per feature after padding;  */
+/*           columns per block group; bytes of LDS of a block; groups = */
+/*           the grid's y).  Needs no device.                           */
+/* Calls without features return SA_OK after the checks of the scalars  */
+/* and look at no pointer; without rows x and queries are not looked at */
+/* and the outputs are still written.  Other element types, q outside   */
+/* 1 .. SA_BIN_MAX_Q, n_abnormal outside 0 .. SA_BIN_MAX_ABNORMAL, rows */
+/* >= 2^40, F >= 2^16, null and misaligned pointers are refused before  */
+/* any launch.  Everything is stream-ordered, allocates nothing, never  */
+/* synchronises with the host and can be captured.  ABI version 3       */
+/* (additive).                                                          */
+/* ------------------------------------------------------------------ */
+#define SA_BIN_MAX_Q 255
+#define SA_BIN_REG_MAX_Q 16
+#define SA_BIN_MAX_ABNORMAL 4
+
+int sa_bin_geometry(int q, uint64_t n_features, int x_type, int* out5);
+
+int sa_bin_range(const void* x, int x_type, uint64_t rows, uint64_t n_features, const double* abnormal, int n_abnormal,
+                 void* out, void* stream);
+
+int sa_bin_ranks(const void* x, int x_type, uint64_t rows, uint64_t n_features, const double* queries, int q,
+                 const double* abnormal, int n_abnormal, int64_t* ranks_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

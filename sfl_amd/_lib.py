@@ -37,6 +37,7 @@ SA_PPB_MAX_PARTIES = 64
 SA_PPB_FLAG_NEGATIVE, SA_PPB_FLAG_NAN, SA_PPB_FLAG_RANGE, SA_PPB_FLAG_NO_R = 1, 2, 4, 8
 SA_PPB_KEY_BITS = (128, 256, 512, 1024, 2048)
 SA_HIST_MAX_BINS = 255
+SA_BIN_MAX_Q, SA_BIN_REG_MAX_Q, SA_BIN_MAX_ABNORMAL = 255, 16, 4
 ABI_VERSION = 3  # include/sfl_sa.h SA_ABI_VERSION (3: the DP norm / clip follow numpy 1.23.5's float64 scalars)
 TUNING_ABI_OFFSET = 1000  # sa_abi_version() of an SA_ABLATE / SA_TIMING build
 
@@ -64,6 +65,7 @@ EXPORTED = (
     "sa_mask_pack2", "sa_fused_clients_pack2", "sa_decode_pack2",
     "sa_ppb_consts_words", "sa_ppb_encode", "sa_ppb_encrypt", "sa_ppb_add", "sa_ppb_decrypt", "sa_ppb_decode",
     "sa_hist_scratch_bytes", "sa_hist_geometry", "sa_hist_codes", "sa_hist_build", "sa_hist_finish",
+    "sa_bin_geometry", "sa_bin_range", "sa_bin_ranks",
 )
 
 
@@ -218,6 +220,9 @@ def _declare(lib):
     lib.sa_hist_codes.argtypes = [vp, i32, u64, u64, vp, vp, i32, vp, vp]
     lib.sa_hist_build.argtypes = [vp, u64, u64, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]
     lib.sa_hist_finish.argtypes = [vp, i32, u64, i32, vp, i32, i32, i32, vp, vp]
+    lib.sa_bin_geometry.argtypes = [i32, u64, i32, P(C.c_int)]
+    lib.sa_bin_range.argtypes = [vp, i32, u64, u64, P(C.c_double), i32, vp, vp]
+    lib.sa_bin_ranks.argtypes = [vp, i32, u64, u64, vp, i32, P(C.c_double), i32, vp, vp]
     lib.sa_dp_perturb_secure_f32.argtypes = [vp, u64, P(DPSecure), vp, vp]
     lib.sa_chacha20_keystream.argtypes = [P(C.c_uint32), u64, u64, u64, vp, vp]
     lib.sa_chacha20_blocks_host.argtypes = [P(C.c_uint32), u64, u64, u64, P(C.c_uint32)]

@@ -1576,3 +1576,55 @@ def hist_finish(scratch: torch.Tensor, n_nodes: int, n_features: int, bmax: int,
                                    int(k_hess), 1 if use_missing else 0, _ptr(out), C.c_void_p(_stream(scratch))),
             "sa_hist_finish")
     return out
+
+
+# ---------------------------------------------------------------------------
+# HomoBinning (sa_bin_*; preprocessing/binning/homo_binning.py on top)
+# ---------------------------------------------------------------------------
+def bin_geometry(q: int, n_features: int, dtype=torch.float32) -> tuple:
+    """``(form, padded query points, columns per group, LDS bytes of a block,
+    groups)`` of ``bin_ranks`` for ``q`` query points a feature; form 0 keeps
+    them in registers, 1 in LDS; needs no GPU."""
+    out = (C.c_int * 5)()
+    L.check(L.lib().sa_bin_geometry(int(q), int(n_features), _float_xtype("bin_geometry", dtype), out),
+            "sa_bin_geometry")
+    return tuple(out)
+
+
+def _bin_args(what: str, x: torch.Tensor, abnormal) -> tuple:
+    xt = _float_xtype(what, x.dtype)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"{what}: x is a contiguous rows x features tensor")
+    ab = [float(a) for a in abnormal]
+    if len(ab) > L.SA_BIN_MAX_ABNORMAL:
+        raise ValueError(f"{what}: at most {L.SA_BIN_MAX_ABNORMAL} abnormal values")
+    return xt, (C.c_double * L.SA_BIN_MAX_ABNORMAL)(*ab), len(ab)
+
+
+def bin_range(x: torch.Tensor, abnormal: Sequence[float], out: torch.Tensor) -> torch.Tensor:
+    """``out`` (int64, ``F x 4``) = per feature of the ``rows x F`` tensor ``x``
+    the float64 bits of min and max over its valid values, their count and the
+    count of NaN.  See sa_bin_range in include/sfl_sa.h."""
+    _require_gpu(x, out)
+    xt, ab, na = _bin_args("bin_range", x, abnormal)
+    rows, nf = x.shape
+    _hist_vec("bin_range", "out", out, torch.int64, 4 * nf, x)
+    L.check(L.lib().sa_bin_range(_ptr(x), xt, rows, nf, ab, na, _ptr(out), C.c_void_p(_stream(x))), "sa_bin_range")
+    return out
+
+
+def bin_ranks(x: torch.Tensor, queries: torch.Tensor, abnormal: Sequence[float], ranks_out: torch.Tensor) -> torch.Tensor:
+    """``ranks_out`` (int64, ``F x Q``) = the number of valid ``x[:, f]`` strictly
+    below ``queries[f, j]`` (float64, ``F x Q``, ascending per feature).  See
+    sa_bin_ranks in include/sfl_sa.h."""
+    _require_gpu(x, queries, ranks_out)
+    xt, ab, na = _bin_args("bin_ranks", x, abnormal)
+    rows, nf = x.shape
+    if queries.dim() != 2 or queries.shape[0] != nf:
+        raise ValueError("bin_ranks: queries is features x Q")
+    q = queries.shape[1]
+    _hist_vec("bin_ranks", "queries", queries, torch.float64, nf * q, x)
+    _hist_vec("bin_ranks", "ranks_out", ranks_out, torch.int64, nf * q, x)
+    L.check(L.lib().sa_bin_ranks(_ptr(x), xt, rows, nf, _ptr(queries), q, ab, na, _ptr(ranks_out),
+                                 C.c_void_p(_stream(x))), "sa_bin_ranks")
+    return ranks_out
