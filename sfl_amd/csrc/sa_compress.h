@@ -1,13 +1,16 @@
 // sa_compress.h — what the compression translation units share (sa_stc.hip,
 // sa_scr.hip, sa_coo.hip, sa_topk.hip, and through sa_runs.h sa_quant.hip and
-// sa_kmeans.hip; sa_flame.hip and sa_flame_wide.hip, the robust aggregator's passes, take the wave
-// layout and the entry checks too, sa_mars.hip the entry checks; nothing else includes it; sa_stc.hip and sa_topk.hip add
-// sa_select.h, the radix select): the block
-// shape, the contiguous wave layout with its launch geometry and the block
-// scan on the device; the element-type dispatch and the first checks of an
-// entry on the host.  A new compressor starts from here.  (The wave sums stay
-// loops in their kernels: behind a function the compiler schedules them
-// differently.)
+// sa_kmeans.hip; sa_stc.hip and sa_topk.hip add sa_select.h, the radix
+// select): the block shape, the contiguous wave layout with its launch
+// geometry and the block scan on the device; the element-type dispatch and
+// the first checks of an entry on the host.  A new compressor starts from
+// here.  (The wave sums stay loops in their kernels: behind a function the
+// compiler schedules them differently.)
+// The robust aggregators' translation units include it too and nothing else
+// does: sa_flame.hip and sa_flame_wide.hip (through sa_flame_keys.h) for the
+// wave layout and the entry checks, sa_mars.hip and sa_freq.hip for the entry
+// checks; the four share check_clients and take_table, the client count and
+// the tables of per-client device pointers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -112,6 +115,43 @@ inline int check_n(uint64_t n, int bits, const char* what, const char* why = "")
 inline int check_float_n(int t, uint64_t n, int bits, const char* what, const char* why = "") {
   const int rc = check_float(t, what);
   return rc != SA_OK ? rc : check_n(n, bits, what, why);
+}
+
+// SA_OK, or SA_ERR_ARG with "<what>: n_clients must be in <lo>..<hi> (<note>)" set
+inline int check_clients(int n_clients, int lo, int hi, const char* what, const char* note = "SA_FLAME_MAX_CLIENTS") {
+  if (n_clients < lo || n_clients > hi) {
+    sa_set_error("%s: n_clients must be in %d..%d (%s)", what, lo, hi, note);
+    return SA_ERR_ARG;
+  }
+  return SA_OK;
+}
+
+// SA_OK, or SA_ERR_ARG set: client c's device pointer of argument `name` is required, element-aligned
+inline int check_client(const void* p, uintptr_t esz, const char* what, int c, const char* name) {
+  if (!p || misaligned(p, esz)) {
+    sa_set_error("%s: bad arguments (client %d's %s is required, element-aligned)", what, c, name);
+    return SA_ERR_ARG;
+  }
+  return SA_OK;
+}
+
+// One argument's host table of device pointers, a client each, into the
+// kernels' by-value array `into`; their addresses are OR-ed into *ptrs (what
+// wave_grid takes) where given.  An entry whose own message names a missing
+// table has refused it before: then only the clients' checks are left.
+inline int take_table(const void* const* t, int n_clients, uintptr_t esz, const void** into, const char* what,
+                      const char* name, uintptr_t* ptrs = nullptr) {
+  if (!t) {
+    sa_set_error("%s: bad arguments (%s is required)", what, name);
+    return SA_ERR_ARG;
+  }
+  for (int c = 0; c < n_clients; c++) {
+    const int rc = check_client(t[c], esz, what, c, name);
+    if (rc != SA_OK) return rc;
+    into[c] = t[c];
+    if (ptrs) *ptrs |= (uintptr_t)t[c];
+  }
+  return SA_OK;
 }
 
 // f(T()) with T the element type of x_type (checked before): float or double

@@ -39,14 +39,8 @@ constexpr int kMaxC = SA_FLAME_MAX_CLIENTS;
 // (DESIGN.md §19 has the resource report this was decided by)
 constexpr int kFusedClients = 8;
 
-// the kernels' by-value arguments: no device allocation holds the pointer table
-struct Ptrs {
-  const void* p[kMaxC];
-};
-struct CombineArgs {
-  const void* p[kMaxC];
-  double s[kMaxC], w[kMaxC];
-};
+typedef ClientPtrs<kMaxC> Ptrs;
+typedef ClientArgs<kMaxC> CombineArgs;
 
 // the rows the first pass takes: all of them up to kFusedClients, else about
 // half of the matrix's entries
@@ -57,30 +51,10 @@ __host__ __device__ constexpr int first_rows(int c) {
   return r;
 }
 
-// --- the sorting network --------------------------------------------------------
-// Batcher's odd-even merge sort of C values as a list of compare-exchanges
-// (lo, hi), lo < hi: the network of the next power of two without the
-// exchanges that touch an index >= C (those values would be +infinity and
-// never move).  63 exchanges at C = 16.
-constexpr int kMaxExchanges = 64;
-struct Net {
-  int n;
-  int lo[kMaxExchanges], hi[kMaxExchanges];
-};
-template <int C>
-constexpr Net make_net() {
-  Net net = {};
-  for (int p = 1; p < C; p *= 2)
-    for (int k = p; k >= 1; k /= 2)
-      for (int j = k % p; j + k < C; j += 2 * k)
-        for (int i = 0; i < k && i + j + k < C; i++)
-          if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) net.lo[net.n] = i + j, net.hi[net.n] = i + j + k, net.n++;
-  return net;
-}
-
+// --- the median: sa_flame_keys.h's network, every exchange a constant pair -----
 template <int C, class K, size_t... I>
 __device__ __forceinline__ void sort_keys(K (&v)[C], std::index_sequence<I...>) {
-  constexpr Net net = make_net<C>();
+  constexpr Net net = batcher<C>();
   auto exchange = [](K& a, K& b) {
     const K lo = a < b ? a : b, hi = a < b ? b : a;
     a = lo, b = hi;
@@ -97,7 +71,7 @@ __device__ __forceinline__ T median_of(const T (&x)[C]) {
   bool nan = false;
 #pragma unroll
   for (int c = 0; c < C; c++) k[c] = to_key(x[c]), nan |= x[c] != x[c];
-  sort_keys<C, K>(k, std::make_index_sequence<make_net<C>().n>());
+  sort_keys<C, K>(k, std::make_index_sequence<batcher<C>().n>());
   T g;
   if constexpr (C % 2) {
     g = from_key<T>(k[C / 2]);
@@ -257,55 +231,28 @@ static void dispatch_clients(int c, F&& f) {
 #undef SA_FLAME_CASE
 }
 
-static int check_clients(int n_clients, const char* what) {
-  if (n_clients < 1 || n_clients > kMaxC) {
-    sa_set_error("%s: n_clients must be in 1..%d (SA_FLAME_MAX_CLIENTS)", what, kMaxC);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
 }  // namespace flame
 }  // namespace sa
 
 using namespace sa::flame;
 
 extern "C" int sa_flame_scratch_bytes(uint64_t n, int n_clients, int x_type) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_scratch_bytes");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_scratch_bytes");
+  const int rc = check_scalars(x_type, n, n_clients, kNarrow, "sa_flame_scratch_bytes");
   if (rc != SA_OK) return rc;
   return (int)(wave_grid(n, 0).grid * stat_count(n_clients) * sizeof(double));
 }
 
 extern "C" int sa_flame_stats(const void* const* x, int n_clients, int x_type, uint64_t n, void* median_out,
                               void* scratch, double* stats, int accumulate, void* stream) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_stats");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_stats");
+  Ptrs px = {};
+  uintptr_t ptrs = (uintptr_t)median_out;
+  const int rc = check_stats(x, n_clients, x_type, n, median_out, scratch, stats, kNarrow, "sa_flame_stats", px.p, &ptrs);
   if (rc != SA_OK) return rc;
-  const uintptr_t esz = elem_size(x_type);
-  if (!stats || misaligned(stats, 8)) {
-    sa_set_error("sa_flame_stats: bad arguments (stats is required, 8-byte aligned)");
-    return SA_ERR_ARG;
-  }
   const int S = stat_count(n_clients);
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) {  // nothing to add; a store is a store of zeros
     if (!accumulate) SA_HIP_CHECK(hipMemsetAsync(stats, 0, S * sizeof(double), st));
     return SA_OK;
-  }
-  if (!x || !median_out || !scratch || misaligned(median_out, esz) || misaligned(scratch, 8)) {
-    sa_set_error("sa_flame_stats: bad arguments (x, median_out and scratch are required; element-aligned "
-                 "median_out, 8-byte aligned scratch)");
-    return SA_ERR_ARG;
-  }
-  Ptrs px = {};
-  uintptr_t ptrs = (uintptr_t)median_out;
-  for (int c = 0; c < n_clients; c++) {
-    if (!x[c] || misaligned(x[c], esz)) {
-      sa_set_error("sa_flame_stats: bad arguments (client %d's tensor is required, element-aligned)", c);
-      return SA_ERR_ARG;
-    }
-    px.p[c] = x[c], ptrs |= (uintptr_t)x[c];
   }
   const Grid g = wave_grid(n, ptrs);
   dispatch_float(x_type, [&](auto t) {
@@ -320,37 +267,12 @@ extern "C" int sa_flame_stats(const void* const* x, int n_clients, int x_type, u
 extern "C" int sa_flame_combine(const void* const* x, const double* scale, const double* weight, int n_clients,
                                 int x_type, uint64_t n, const void* median, double divisor, double* out,
                                 void* stream) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_combine");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_combine");
-  if (rc != SA_OK) return rc;
-  const uintptr_t esz = elem_size(x_type);
-  if (!x || !scale || !weight) {
-    sa_set_error("sa_flame_combine: bad arguments (x, scale and weight are required)");
-    return SA_ERR_ARG;
-  }
-  // a dropped client (its weight is a NaN) is left out here: its pointer never reaches the kernel
   CombineArgs a = {};
   uintptr_t ptrs = (uintptr_t)median | (uintptr_t)out;
   int kept = 0;
-  for (int c = 0; c < n_clients; c++) {
-    if (weight[c] != weight[c]) continue;
-    if (n && (!x[c] || misaligned(x[c], esz))) {
-      sa_set_error("sa_flame_combine: bad arguments (client %d's tensor is required, element-aligned)", c);
-      return SA_ERR_ARG;
-    }
-    a.p[kept] = x[c], a.s[kept] = scale[c], a.w[kept] = weight[c], ptrs |= (uintptr_t)x[c];
-    kept++;
-  }
-  if (kept == 0) {
-    sa_set_error("sa_flame_combine: every client is dropped (a NaN weight drops a client)");
-    return SA_ERR_ARG;
-  }
-  if (n == 0) return SA_OK;
-  if (!median || !out || misaligned(median, esz) || misaligned(out, 8)) {
-    sa_set_error("sa_flame_combine: bad arguments (median and out are required; element-aligned median, 8-byte "
-                 "aligned out)");
-    return SA_ERR_ARG;
-  }
+  const int rc = check_combine(x, scale, weight, n_clients, x_type, n, median, out, kNarrow, "sa_flame_combine", &a,
+                               &kept, &ptrs);
+  if (rc != SA_OK || n == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   const Grid g = wave_grid(n, ptrs);
   dispatch_float(x_type, [&](auto t) {

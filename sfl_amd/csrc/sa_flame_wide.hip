@@ -44,7 +44,7 @@ using namespace sa::wave;
 
 typedef double double4 __attribute__((ext_vector_type(4)));  // the matrix instruction's accumulator
 
-constexpr int kMinC = SA_FLAME_MAX_CLIENTS + 1, kMaxC = SA_FLAME_WIDE_MAX_CLIENTS;
+constexpr int kMaxC = SA_FLAME_WIDE_MAX_CLIENTS;
 constexpr int kE = 128;                 // elements a tile
 constexpr int kCols = kE / kWaves;      // a wave's share of a tile's k dimension
 constexpr int kStatBlocks = 512;        // 2 resident blocks per CU on 256 CUs
@@ -68,14 +68,9 @@ __host__ __device__ constexpr int tile_count(int cp) { return (cp / 16) * (cp / 
 // register r, lane: [q * 256 + r * 64 + lane]), then CP values of N
 __host__ __device__ constexpr int partial_count(int cp) { return tile_count(cp) * 256 + cp; }
 
-// the kernels' by-value arguments: no device allocation holds the pointer table
-struct Ptrs {
-  const void* p[kMaxC];
-};
-struct CombineArgs {
-  const void* p[kMaxC];
-  double s[kMaxC], w[kMaxC];
-  int kept;
+typedef ClientPtrs<kMaxC> Ptrs;
+struct CombineArgs : ClientArgs<kMaxC> {
+  int kept;  // the clients are a run-time loop here
 };
 
 // the launch of the statistics pass: a function of n only
@@ -91,25 +86,14 @@ inline StatGrid stat_grid(uint64_t n) {
 }
 
 // --- the sorting network --------------------------------------------------------
-// Batcher's odd-even merge sort of CP values (a power of two) as a list of
-// compare-exchanges (lo, hi), without those from which neither middle output
-// (CP/2 - 1, CP/2) can be reached, filled up to a multiple of kChunk with
-// exchanges of value 0 with itself (nothing).  543 exchanges at CP = 64, 191
-// at 32, before the pruning.
+// sa_flame_keys.h's network of CP values (a power of two) without the
+// exchanges from which neither middle output (CP/2 - 1, CP/2) can be reached,
+// filled up to a multiple of kChunk with exchanges of value 0 with itself
+// (nothing).  543 exchanges at CP = 64, 191 at 32, before the pruning.
 constexpr int kChunk = 64;
-constexpr int kMaxExchanges = 576;
-struct Net {
-  int n;
-  short lo[kMaxExchanges], hi[kMaxExchanges];
-};
 template <int CP>
 constexpr Net make_net() {
-  Net all = {};
-  for (int p = 1; p < CP; p *= 2)
-    for (int k = p; k >= 1; k /= 2)
-      for (int j = k % p; j + k < CP; j += 2 * k)
-        for (int i = 0; i < k && i + j + k < CP; i++)
-          if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) all.lo[all.n] = i + j, all.hi[all.n] = i + j + k, all.n++;
+  const Net all = batcher<CP>();
   bool need[CP] = {}, keep[kMaxExchanges] = {};
   need[CP / 2 - 1] = need[CP / 2] = true;
   for (int q = all.n - 1; q >= 0; q--)
@@ -383,51 +367,24 @@ __global__ void __launch_bounds__(kBlock) k_combine_wide(const CombineArgs a, ui
   }
 }
 
-static int check_clients(int n_clients, const char* what) {
-  if (n_clients < kMinC || n_clients > kMaxC) {
-    sa_set_error("%s: n_clients must be in %d..%d (SA_FLAME_WIDE_MAX_CLIENTS; 1..%d: the sa_flame_* entries)", what,
-                 kMinC, kMaxC, kMinC - 1);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
 }  // namespace flame_wide
 }  // namespace sa
 
 using namespace sa::flame_wide;
 
 extern "C" int sa_flame_wide_scratch_bytes(uint64_t n, int n_clients, int x_type) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_wide_scratch_bytes");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_wide_scratch_bytes");
+  const int rc = check_scalars(x_type, n, n_clients, kWide, "sa_flame_wide_scratch_bytes");
   if (rc != SA_OK) return rc;
   return (int)(stat_grid(n).grid * partial_count(padded(n_clients)) * sizeof(double));
 }
 
 extern "C" int sa_flame_stats_wide(const void* const* x, int n_clients, int x_type, uint64_t n, void* median_out,
                                    void* scratch, double* stats, int accumulate, void* stream) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_stats_wide");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_stats_wide");
-  if (rc != SA_OK) return rc;
-  const uintptr_t esz = elem_size(x_type);
-  if (!stats || misaligned(stats, 8)) {
-    sa_set_error("sa_flame_stats_wide: bad arguments (stats is required, 8-byte aligned)");
-    return SA_ERR_ARG;
-  }
-  if (n && (!x || !median_out || !scratch || misaligned(median_out, esz) || misaligned(scratch, 8))) {
-    sa_set_error("sa_flame_stats_wide: bad arguments (x, median_out and scratch are required; element-aligned "
-                 "median_out, 8-byte aligned scratch)");
-    return SA_ERR_ARG;
-  }
   Ptrs px = {};
   uintptr_t ptrs = 0;
-  for (int c = 0; n && c < n_clients; c++) {
-    if (!x[c] || misaligned(x[c], esz)) {
-      sa_set_error("sa_flame_stats_wide: bad arguments (client %d's tensor is required, element-aligned)", c);
-      return SA_ERR_ARG;
-    }
-    px.p[c] = x[c], ptrs |= (uintptr_t)x[c];
-  }
+  const int rc = check_stats(x, n_clients, x_type, n, median_out, scratch, stats, kWide, "sa_flame_stats_wide", px.p,
+                             &ptrs);
+  if (rc != SA_OK) return rc;
   const int CP = padded(n_clients), S = stat_count(n_clients);
   const StatGrid g = stat_grid(n);
   hipStream_t st = (hipStream_t)stream;
@@ -454,36 +411,11 @@ extern "C" int sa_flame_stats_wide(const void* const* x, int n_clients, int x_ty
 extern "C" int sa_flame_combine_wide(const void* const* x, const double* scale, const double* weight, int n_clients,
                                      int x_type, uint64_t n, const void* median, double divisor, double* out,
                                      void* stream) {
-  int rc = check_float_n(x_type, n, 32, "sa_flame_combine_wide");
-  if (rc == SA_OK) rc = check_clients(n_clients, "sa_flame_combine_wide");
-  if (rc != SA_OK) return rc;
-  const uintptr_t esz = elem_size(x_type);
-  if (!x || !scale || !weight) {
-    sa_set_error("sa_flame_combine_wide: bad arguments (x, scale and weight are required)");
-    return SA_ERR_ARG;
-  }
-  // a dropped client (its weight is a NaN) is left out here: its pointer never reaches the kernel
   CombineArgs a = {};
   uintptr_t ptrs = (uintptr_t)median | (uintptr_t)out;
-  for (int c = 0; c < n_clients; c++) {
-    if (weight[c] != weight[c]) continue;
-    if (n && (!x[c] || misaligned(x[c], esz))) {
-      sa_set_error("sa_flame_combine_wide: bad arguments (client %d's tensor is required, element-aligned)", c);
-      return SA_ERR_ARG;
-    }
-    a.p[a.kept] = x[c], a.s[a.kept] = scale[c], a.w[a.kept] = weight[c], ptrs |= (uintptr_t)x[c];
-    a.kept++;
-  }
-  if (a.kept == 0) {
-    sa_set_error("sa_flame_combine_wide: every client is dropped (a NaN weight drops a client)");
-    return SA_ERR_ARG;
-  }
-  if (n == 0) return SA_OK;
-  if (!median || !out || misaligned(median, esz) || misaligned(out, 8)) {
-    sa_set_error("sa_flame_combine_wide: bad arguments (median and out are required; element-aligned median, 8-byte "
-                 "aligned out)");
-    return SA_ERR_ARG;
-  }
+  const int rc = check_combine(x, scale, weight, n_clients, x_type, n, median, out, kWide, "sa_flame_combine_wide", &a,
+                               &a.kept, &ptrs);
+  if (rc != SA_OK || n == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   const Grid g = wave_grid(n, ptrs);
   dispatch_float(x_type, [&](auto t) {

@@ -204,18 +204,10 @@ __global__ void __launch_bounds__(wave::kBlock) k_gram(const double* __restrict_
 }
 
 // --- the entries' checks ----------------------------------------------------------------
-static int check_clients(int n_clients, const char* what) {
-  if (n_clients < 0 || n_clients > kMaxC) {
-    sa_set_error("%s: n_clients must be in 0..%d (SA_FLAME_MAX_CLIENTS)", what, kMaxC);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
 // the scalars of a features call; *bytes gets the scratch's size
 static int check_shape(uint64_t rows, uint64_t cols, int n_clients, int x_type, const char* what, uint64_t* bytes) {
   int rc = check_float(x_type, what);
-  if (rc == SA_OK) rc = check_clients(n_clients, what);
+  if (rc == SA_OK) rc = check_clients(n_clients, 0, kMaxC, what);
   if (rc == SA_OK) rc = check_n(rows | cols, 24, what, " (rows, cols)");
   if (rc != SA_OK) return rc;
   if (rows < 2 || cols < 2) {
@@ -263,13 +255,9 @@ extern "C" int sa_freq_features(const void* const* w, int n_clients, int x_type,
   double* A = reinterpret_cast<double*>(scratch);
   double* B = A + c.hk * rows;
   double* Tt = B + c.wk * cols;
-  for (int i = 0; i < n_clients; i++) {
-    if (!w[i] || misaligned(w[i], esz)) {
-      sa_set_error("%s: bad arguments (client %d's w is required, element-aligned)", what, i);
-      return SA_ERR_ARG;
-    }
-    pw.y[i] = w[i], pt.y[i] = Tt + (uint64_t)i * c.wk * rows;
-  }
+  rc = take_table(w, n_clients, esz, pw.y, what, "w");  // (w is there: the check above)
+  if (rc != SA_OK) return rc;
+  for (int i = 0; i < n_clients; i++) pt.y[i] = Tt + (uint64_t)i * c.wk * rows;
   hipStream_t st = (hipStream_t)stream;
   uint64_t blocks = (c.hk * rows + c.wk * cols + sa::wave::kBlock - 1) / sa::wave::kBlock;
   if (blocks > (uint64_t)sa::wave::kMaxBlocks) blocks = sa::wave::kMaxBlocks;
@@ -292,7 +280,7 @@ extern "C" int sa_freq_features(const void* const* w, int n_clients, int x_type,
 extern "C" int sa_freq_gram(const double* feats, int n_clients, uint64_t len, double* out, void* stream) {
   const char* what = "sa_freq_gram";
   int rc = check_n(len, 32, what);
-  if (rc == SA_OK) rc = check_clients(n_clients, what);
+  if (rc == SA_OK) rc = check_clients(n_clients, 0, kMaxC, what);
   if (rc != SA_OK) return rc;
   if (n_clients == 0) return SA_OK;
   if (!feats || !out || misaligned(feats, 8) || misaligned(out, 8)) {

@@ -592,34 +592,9 @@ __global__ void __launch_bounds__(wave::kBlock) k_eig_wide(const Ptrs px, uint64
   }
 }
 
-// the table of one argument: required, element-aligned device pointers
-static int take_table(const void* const* t, int n_clients, uintptr_t esz, const void** into, const char* what,
-                      const char* name) {
-  if (!t) {
-    sa_set_error("%s: bad arguments (%s is required)", what, name);
-    return SA_ERR_ARG;
-  }
-  for (int c = 0; c < n_clients; c++) {
-    if (!t[c] || misaligned(t[c], esz)) {
-      sa_set_error("%s: bad arguments (client %d's %s is required, element-aligned)", what, c, name);
-      return SA_ERR_ARG;
-    }
-    into[c] = t[c];
-  }
-  return SA_OK;
-}
-
-static int check_clients(int n_clients, const char* what) {
-  if (n_clients < 0 || n_clients > kMaxC) {
-    sa_set_error("%s: n_clients must be in 0..%d (SA_FLAME_MAX_CLIENTS)", what, kMaxC);
-    return SA_ERR_ARG;
-  }
-  return SA_OK;
-}
-
 // the scalars of a wide call; *bytes gets the scratch's size
 static int check_wide(int n_clients, uint64_t n_mat, uint64_t rows, uint64_t cols, const char* what, uint64_t* bytes) {
-  int rc = check_clients(n_clients, what);
+  int rc = check_clients(n_clients, 0, kMaxC, what);
   if (rc == SA_OK) rc = check_n(n_mat, 24, what, " matrices (n_mat)");
   if (rc == SA_OK) rc = check_n(rows | cols, 24, what, " (rows, cols)");
   if (rc != SA_OK) return rc;
@@ -695,7 +670,7 @@ extern "C" int sa_mars_sigma(const void* const* w, int n_clients, int x_type, ui
                              double* out, void* stream) {
   const char* what = "sa_mars_sigma";
   int rc = check_float(x_type, what);
-  if (rc == SA_OK) rc = check_clients(n_clients, what);
+  if (rc == SA_OK) rc = check_clients(n_clients, 0, kMaxC, what);
   // one block a matrix: the grid and every matrix's offset stay below 2^31 and 2^63
   if (rc == SA_OK) rc = check_n(n_mat, 24, what, " matrices (n_mat)");
   if (rc == SA_OK) rc = check_n(rows | cols, 24, what, " (rows, cols)");
@@ -742,7 +717,7 @@ extern "C" int sa_mars_bn(const void* const* bn_w, const void* const* bn_var, in
                           uint64_t n_bn, double* out, void* stream) {
   const char* what = "sa_mars_bn";
   int rc = check_float_n(x_type, n_bn, 32, what);
-  if (rc == SA_OK) rc = check_clients(n_clients, what);
+  if (rc == SA_OK) rc = check_clients(n_clients, 0, kMaxC, what);
   if (rc != SA_OK) return rc;
   if (n_clients == 0 || n_bn == 0) return SA_OK;
   if (!out || misaligned(out, 8)) {

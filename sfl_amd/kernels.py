@@ -1145,16 +1145,21 @@ def flame_scratch_bytes(n: int, n_clients: int, dtype: torch.dtype) -> int:
     return _scratch_bytes("flame_scratch_bytes", "sa_flame_scratch_bytes", (n, n_clients), dtype)
 
 
-def _flame_table(what: str, xs: Sequence, like: torch.Tensor) -> C.Array:
-    """The host table of the clients' device pointers.  An entry is a tensor
-    of ``like``'s size and dtype, or -- handed to the library as it is, which
-    refuses what it cannot take -- ``None`` or an address."""
+_LIKE_MEDIAN = "of the median's size, dtype and device"  # how the flame wrappers word _client_table's refusal
+
+
+def _client_table(what: str, name: str, xs: Sequence, numel: int, like: torch.Tensor, fits: str = "") -> C.Array:
+    """The host table of one argument's device pointers, one client each: a
+    contiguous tensor of ``numel`` elements of ``like``'s dtype on its device,
+    or -- handed to the library as it is, which refuses what it cannot take --
+    ``None`` or an address."""
     table = (C.c_void_p * max(1, len(xs)))()
     for i, x in enumerate(xs):
         if isinstance(x, torch.Tensor):
             _require_gpu(x)
-            if x.dtype != like.dtype or x.numel() != like.numel() or not x.is_contiguous() or x.device != like.device:
-                raise ValueError(f"{what}: client {i}'s tensor is contiguous, of the median's size, dtype and device")
+            if x.dtype != like.dtype or x.numel() != numel or not x.is_contiguous() or x.device != like.device:
+                raise ValueError(f"{what}: client {i}'s {name} is contiguous, "
+                                 f"{fits or f'{numel} elements of one dtype on one device'}")
             table[i] = x.data_ptr()
         else:
             table[i] = x
@@ -1162,25 +1167,27 @@ def _flame_table(what: str, xs: Sequence, like: torch.Tensor) -> C.Array:
 
 
 def flame_stats(xs: Sequence, median_out: torch.Tensor, scratch: torch.Tensor, stats: torch.Tensor, *,
-                accumulate: bool = False) -> torch.Tensor:
+                accumulate: bool = False, _entry: str = "sa_flame_stats") -> torch.Tensor:
     """The element-wise median of the clients' tensors ``xs`` into
     ``median_out``; their Gram matrix and squared update norms into ``stats``
     (float64, ``flame_stat_count(len(xs))`` values), added to what is there
     with ``accumulate``.  The client count, the element type and the pointers
     are judged by the library.  See sa_flame_stats in include/sfl_sa.h."""
+    what = _entry[3:]  # the wrapper's name
+    sizer, lo, hi = (flame_scratch_bytes, 1, L.SA_FLAME_MAX_CLIENTS) if _entry == "sa_flame_stats" else \
+        (flame_wide_scratch_bytes, L.SA_FLAME_MAX_CLIENTS + 1, L.SA_FLAME_WIDE_MAX_CLIENTS)
     _require_gpu(median_out, scratch, stats)
     c, n = len(xs), median_out.numel()
     if not median_out.is_contiguous() or not stats.is_contiguous() or stats.dtype != torch.float64:
-        raise ValueError("flame_stats: contiguous tensors; stats is float64")
+        raise ValueError(f"{what}: contiguous tensors; stats is float64")
     xt = _XTYPE.get(median_out.dtype, -1)
-    if 1 <= c <= L.SA_FLAME_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64):
+    if lo <= c <= hi and xt in (L.SA_F32, L.SA_F64):
         if stats.numel() < flame_stat_count(c):
-            raise ValueError("flame_stats: stats smaller than flame_stat_count(len(xs))")
-        _require_scratch("flame_stats", scratch, flame_scratch_bytes(n, c, median_out.dtype),
-                         "flame_scratch_bytes(n, n_clients, dtype)")
-    table = _flame_table("flame_stats", xs, median_out)
-    L.check(L.lib().sa_flame_stats(table, c, xt, n, _ptr(median_out), _ptr(scratch), _ptr(stats), int(bool(accumulate)),
-                                   C.c_void_p(_stream(median_out))), "sa_flame_stats")
+            raise ValueError(f"{what}: stats smaller than flame_stat_count(len(xs))")
+        _require_scratch(what, scratch, sizer(n, c, median_out.dtype), f"{sizer.__name__}(n, n_clients, dtype)")
+    table = _client_table(what, "tensor", xs, n, median_out, _LIKE_MEDIAN)
+    L.check(getattr(L.lib(), _entry)(table, c, xt, n, _ptr(median_out), _ptr(scratch), _ptr(stats),
+                                     int(bool(accumulate)), C.c_void_p(_stream(median_out))), _entry)
     return stats
 
 
@@ -1198,7 +1205,7 @@ def flame_combine(xs: Sequence, scales: Sequence[float], weights: Sequence[float
     if not median.is_contiguous() or not out.is_contiguous() or out.dtype != torch.float64 or out.numel() != n \
             or out.device != median.device:
         raise ValueError("flame_combine: out is contiguous float64 of the median's size, on its device")
-    table = _flame_table("flame_combine", xs, median)
+    table = _client_table("flame_combine", "tensor", xs, n, median, _LIKE_MEDIAN)
     s = (C.c_double * max(1, c))(*[float(v) for v in scales])
     w = (C.c_double * max(1, c))(*[float(v) if k else float("nan") for v, k in zip(weights, keep)])
     L.check(getattr(L.lib(), _entry)(table, s, w, c, _XTYPE.get(median.dtype, -1), n, _ptr(median), float(divisor),
@@ -1216,20 +1223,7 @@ def flame_stats_wide(xs: Sequence, median_out: torch.Tensor, scratch: torch.Tens
     """``flame_stats`` for 17 to ``SA_FLAME_WIDE_MAX_CLIENTS`` clients: the same
     median and the same packed statistics, through ``flame_wide_scratch_bytes``
     bytes of scratch.  See sa_flame_stats_wide in include/sfl_sa.h."""
-    _require_gpu(median_out, scratch, stats)
-    c, n = len(xs), median_out.numel()
-    if not median_out.is_contiguous() or not stats.is_contiguous() or stats.dtype != torch.float64:
-        raise ValueError("flame_stats_wide: contiguous tensors; stats is float64")
-    xt = _XTYPE.get(median_out.dtype, -1)
-    if L.SA_FLAME_MAX_CLIENTS < c <= L.SA_FLAME_WIDE_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64):
-        if stats.numel() < flame_stat_count(c):
-            raise ValueError("flame_stats_wide: stats smaller than flame_stat_count(len(xs))")
-        _require_scratch("flame_stats_wide", scratch, flame_wide_scratch_bytes(n, c, median_out.dtype),
-                         "flame_wide_scratch_bytes(n, n_clients, dtype)")
-    table = _flame_table("flame_stats_wide", xs, median_out)
-    L.check(L.lib().sa_flame_stats_wide(table, c, xt, n, _ptr(median_out), _ptr(scratch), _ptr(stats),
-                                        int(bool(accumulate)), C.c_void_p(_stream(median_out))), "sa_flame_stats_wide")
-    return stats
+    return flame_stats(xs, median_out, scratch, stats, accumulate=accumulate, _entry="sa_flame_stats_wide")
 
 
 def flame_combine_wide(xs: Sequence, scales: Sequence[float], weights: Sequence[float], keep: Sequence[bool],
@@ -1242,23 +1236,6 @@ def flame_combine_wide(xs: Sequence, scales: Sequence[float], weights: Sequence[
 # ---------------------------------------------------------------------------
 # MarsAggregator (sa_mars_*; security/aggregation/mars_aggregator.py on top)
 # ---------------------------------------------------------------------------
-def _mars_table(what: str, name: str, xs: Sequence, numel: int, like: torch.Tensor) -> C.Array:
-    """The host table of one argument's device pointers, one client each: a
-    contiguous tensor of ``numel`` elements of ``like``'s dtype on its device,
-    or -- handed to the library as it is, which refuses what it cannot take --
-    ``None`` or an address."""
-    table = (C.c_void_p * max(1, len(xs)))()
-    for i, x in enumerate(xs):
-        if isinstance(x, torch.Tensor):
-            _require_gpu(x)
-            if x.dtype != like.dtype or x.numel() != numel or not x.is_contiguous() or x.device != like.device:
-                raise ValueError(f"{what}: client {i}'s {name} is contiguous, {numel} elements of one dtype on one device")
-            table[i] = x.data_ptr()
-        else:
-            table[i] = x
-    return table
-
-
 def _mars_out(what: str, out: torch.Tensor, offset: int, count: int) -> C.c_void_p:
     _require_gpu(out)
     if out.dtype != torch.float64 or not out.is_contiguous() or offset < 0 or offset + count > out.numel():
@@ -1299,9 +1276,9 @@ def _mars_sigma_args(what: str, ws: Sequence, n_mat: int, rows: int, cols: int, 
     if len(bn_w):
         first = _mars_like(what, bn_w)
         n_bn = first.numel()
-    table = _mars_table(what, "tensor", ws, n_mat * rows * cols, like)
-    tw = _mars_table(what, "bn_w", bn_w, n_bn, like) if n_bn else None
-    tv = _mars_table(what, "bn_var", bn_var, n_bn, like) if n_bn else None
+    table = _client_table(what, "tensor", ws, n_mat * rows * cols, like)
+    tw = _client_table(what, "bn_w", bn_w, n_bn, like) if n_bn else None
+    tv = _client_table(what, "bn_var", bn_var, n_bn, like) if n_bn else None
     return ((table, c, _XTYPE.get(like.dtype, -1), int(n_mat), int(rows), int(cols), tw, tv, n_bn),
             (_mars_out(what, out, offset, c * n_mat), C.c_void_p(_stream(like))))
 
@@ -1338,8 +1315,8 @@ def mars_bn(bn_w: Sequence, bn_var: Sequence, out: torch.Tensor, offset: int = 0
     if len(bn_var) != c:
         raise ValueError("mars_bn: one bn_w and one bn_var per client")
     n_bn = like.numel()
-    tw = _mars_table("mars_bn", "bn_w", bn_w, n_bn, like)
-    tv = _mars_table("mars_bn", "bn_var", bn_var, n_bn, like)
+    tw = _client_table("mars_bn", "bn_w", bn_w, n_bn, like)
+    tv = _client_table("mars_bn", "bn_var", bn_var, n_bn, like)
     L.check(L.lib().sa_mars_bn(tw, tv, c, _XTYPE.get(like.dtype, -1), n_bn, _mars_out("mars_bn", out, offset, c * n_bn),
                                C.c_void_p(_stream(like))), "sa_mars_bn")
     return out
@@ -1375,7 +1352,7 @@ def freq_features(ws: Sequence, rows: int, cols: int, scratch: torch.Tensor, fea
     if 1 <= c <= L.SA_FLAME_MAX_CLIENTS and xt in (L.SA_F32, L.SA_F64) and rows >= 2 and cols >= 2:
         _require_scratch("freq_features", scratch, freq_scratch_bytes(rows, cols, c, like.dtype),
                          "freq_scratch_bytes(rows, cols, n_clients, dtype)")
-    table = _mars_table("freq_features", "tensor", ws, rows * cols, like)
+    table = _client_table("freq_features", "tensor", ws, rows * cols, like)
     L.check(L.lib().sa_freq_features(table, c, xt, int(rows), int(cols), _ptr(scratch), _ptr(feats_out),
                                      C.c_void_p(_stream(like))), "sa_freq_features")
     return feats_out

@@ -68,10 +68,9 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from ...device import PYU, DeviceObject
-from .aggregator import Aggregator
+from ...device import PYU
+from .robust import _FLOATS, RobustAggregator, _host, _layers, _weights, upload
 
-_FLOATS = (np.dtype(np.float32), np.dtype(np.float64))
 MAX_DEVICE_CLIENTS = 16  # SA_FLAME_MAX_CLIENTS: the kernels' client count is a template argument
 WIDE_MAX_DEVICE_CLIENTS = 64  # SA_FLAME_WIDE_MAX_CLIENTS: the client count padded to 32 or 64 in LDS
 
@@ -219,51 +218,7 @@ def flame_host(data: Sequence[Sequence[np.ndarray]], weights=None) -> tuple:
     return [combine_host(xs, g, report["scales"], w, keep) for xs, g in zip(layers, medians)], report
 
 
-# ------------------------------------------------------------- arguments
-def _weights(weights, C: int) -> List[float]:
-    if weights is None:
-        return [1.0] * C
-    if not isinstance(weights, (list, tuple)) or len(weights) != C:
-        raise ValueError(f"weights: one scalar per client ({C}) or None")
-    out = []
-    for i, v in enumerate(weights):
-        v = _host(v)  # (a device scalar: through a pinned buffer)
-        if v.ndim != 0 or v.dtype.kind not in "fiub":
-            raise ValueError(f"weights: client {i}'s weight is not one number (per-element weights are not FLAME's)")
-        if not np.isfinite(v):
-            raise ValueError(f"weights: client {i}'s weight is not finite")
-        out.append(float(v))
-    return out
-
-
-def _layers(data: list) -> list:
-    """``data[i][l]`` -> ``layers[l][i]``, with one shape and one float type per layer."""
-    L0 = len(data[0])
-    for i, d in enumerate(data):
-        if len(d) != L0:
-            raise ValueError(f"client {i} uploads {len(d)} layers, client 0 uploads {L0}")
-    layers = [[d[l] for d in data] for l in range(L0)]
-    for l, xs in enumerate(layers):
-        shape, dtype = tuple(xs[0].shape), _np_dtype(xs[0])
-        if dtype not in _FLOATS:
-            raise ValueError(f"layer {l}, client 0: float32 or float64, not {xs[0].dtype}")
-        for i, x in enumerate(xs):
-            if tuple(x.shape) != shape or _np_dtype(x) != dtype:
-                raise ValueError(f"layer {l}, client {i}: shape {tuple(x.shape)} and type {x.dtype} differ from "
-                                 f"client 0's {shape} and {xs[0].dtype}")
-    return layers
-
-
-_TORCH_FLOATS = {torch.float32: _FLOATS[0], torch.float64: _FLOATS[1]}
-
-
-def _np_dtype(x):
-    """The numpy type of a layer; a tensor of a type FLAME does not take keeps its
-    torch type, which equals no numpy type (None would: numpy reads it as float64)."""
-    return _TORCH_FLOATS.get(x.dtype, x.dtype) if isinstance(x, torch.Tensor) else np.dtype(x.dtype)
-
-
-class FlameAggregator(Aggregator):
+class FlameAggregator(RobustAggregator):
     """FLAME aggregator (Byzantine-robust aggregation).
 
     The computation is performed in plaintext: every party's update reaches
@@ -291,13 +246,11 @@ class FlameAggregator(Aggregator):
     """
 
     def __init__(self, device: PYU, wide_clients=None):
-        assert isinstance(device, PYU), f"Accepts PYU only but got {type(device)}."
+        super().__init__(device)
         if wide_clients not in (None, "device"):
             raise ValueError(f'wide_clients is None (more than {MAX_DEVICE_CLIENTS} device clients are refused) or '
                              f'"device", not {wide_clients!r}')
-        self.device = device
         self.wide_clients = wide_clients
-        self.last_report = None
 
     # ------------------------------------------------------------ the paths
     def _device_average(self, layers: list, w: List[float], dev) -> list:
@@ -306,26 +259,12 @@ class FlameAggregator(Aggregator):
 
         C = len(layers[0])
         wide = C > MAX_DEVICE_CLIENTS and self.wide_clients == "device"
-        if wide and C > WIDE_MAX_DEVICE_CLIENTS:
-            raise NotImplementedError(f"FlameAggregator takes at most {WIDE_MAX_DEVICE_CLIENTS} clients on the device "
-                                      f"(SA_FLAME_WIDE_MAX_CLIENTS), got {C}; the host form takes any number")
-        if C > MAX_DEVICE_CLIENTS and not wide:
-            raise NotImplementedError(f"FlameAggregator takes at most {MAX_DEVICE_CLIENTS} clients on the device "
-                                      f"(SA_FLAME_MAX_CLIENTS), got {C}; the host form takes any number")
+        limit, macro = (MAX_DEVICE_CLIENTS, "SA_FLAME_MAX_CLIENTS") if self.wide_clients is None else \
+            (WIDE_MAX_DEVICE_CLIENTS, "SA_FLAME_WIDE_MAX_CLIENTS")
+        on_dev = upload(layers, dev, "FlameAggregator", limit, macro)
         scratch_bytes, stats_pass, combine_pass = \
             (K.flame_wide_scratch_bytes, K.flame_stats_wide, K.flame_combine_wide) if wide else \
             (K.flame_scratch_bytes, K.flame_stats, K.flame_combine)
-        on_dev = []
-        for l, xs in enumerate(layers):
-            row = []
-            for i, x in enumerate(xs):
-                if isinstance(x, torch.Tensor) and x.is_cuda:
-                    if x.device != dev:
-                        raise ValueError(f"layer {l}, client {i}: on {x.device}, the others on {dev}")
-                    row.append(x.detach().contiguous().reshape(-1))
-                else:  # a host layer among device ones: through pinned memory
-                    row.append(H.h2d(x, dev).reshape(-1))
-            on_dev.append(row)
         stats = torch.zeros(K.flame_stat_count(C), dtype=torch.float64, device=dev)
         need = max(scratch_bytes(r[0].numel(), C, r[0].dtype) for r in on_dev)
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -355,69 +294,15 @@ class FlameAggregator(Aggregator):
         return outs
 
     def _average(self, parties: list, weights):
-        single = not isinstance(parties[0], (list, tuple))
-        data = [[p] if single else list(p) for p in parties]
-        data = [[x if isinstance(x, torch.Tensor) else np.asarray(x) for x in d] for d in data]
-        for i, d in enumerate(data):
-            for l, x in enumerate(d):
-                if type(x).__name__ == "SparseCOO" or x.dtype == object:
-                    raise ValueError(f"layer {l}, client {i}: FlameAggregator takes dense float layers (sparse "
-                                     f"uploads: SparsePlainAggregator)")
-        C = len(data)
-        w = _weights(weights, C)
-        layers = _layers(data)
-        dev = next((x.device for xs in layers for x in xs if isinstance(x, torch.Tensor) and x.is_cuda), None)
+        single, data, layers, w, dev = self._parse(parties, weights)
         if dev is not None:
             outs = self._device_average(layers, w, dev)
         else:
-            host = [[x.detach().numpy() if isinstance(x, torch.Tensor) else x for x in xs] for xs in layers]
+            host = [[_host(x) for x in xs] for xs in layers]
             medians = [median_host(np.stack(xs)) for xs in host]
-            report = decide(stats_host(host, medians), C)
+            report = decide(stats_host(host, medians), len(data))
             keep = [lb == 0 for lb in report["labels"]]
             outs = [combine_host(xs, g, report["scales"], w, keep) for xs, g in zip(host, medians)]
             self.last_report = report
         log.info("Cluster labels: %s", self.last_report["labels"])
         return outs[0] if single else outs
-
-    # --------------------------------------------------------------- surface
-    def _run(self, data: List[DeviceObject], fn):
-        assert data, "Data to aggregate should not be None or empty!"
-        data = [d.to(self.device) for d in data]
-        return self.device(fn)(*data)
-
-    def sum(self, data: List[DeviceObject], axis=None) -> DeviceObject:
-        """Sum of array elements over a given axis (the reference inherits
-        ``PlainAggregator.sum`` unchanged: ``np.sum`` over the stacked parties,
-        per layer for per-layer lists).  Device float64 layers summed over the
-        parties stay on the device (``kernels.sum_f64``); other device layers
-        are read to the host."""
-        def one(xs):
-            if axis == 0 and all(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 for x in xs) \
-                    and all(x.shape == xs[0].shape and x.device == xs[0].device for x in xs):
-                from ... import kernels as K
-
-                return K.sum_f64([x.detach().contiguous() for x in xs], torch.empty_like(xs[0].contiguous()))
-            return np.sum([_host(x) for x in xs], axis=axis)
-
-        def _sum(*parties):
-            if isinstance(parties[0], (list, tuple)):
-                return [one(list(layer)) for layer in zip(*parties)]
-            return one(list(parties))
-
-        return self._run(data, _sum)
-
-    def average(self, data: List[DeviceObject], axis=None, weights=None) -> DeviceObject:
-        """The robust average over the parties (the module's definition)."""
-        if axis not in (None, 0):
-            raise ValueError(f"FlameAggregator aggregates over the parties (axis 0 or None), not axis {axis}")
-        if isinstance(weights, (list, tuple)):
-            weights = [wt.to(self.device).data if isinstance(wt, DeviceObject) else wt for wt in weights]
-        return self._run(data, lambda *parties: self._average(list(parties), weights))
-
-
-def _host(x):
-    if isinstance(x, torch.Tensor):
-        from ... import hostpipe as H
-
-        return H.d2h(x, pooled=False) if x.is_cuda else x.detach().numpy()
-    return np.asarray(x)

@@ -82,9 +82,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from ...device import PYU
-from .flame_aggregator import FlameAggregator, _layers, _weights
-from .mars_aggregator import _one_type, average_kept, combine_host, upload
+from .robust import RobustAggregator, _host, _layers, _one_type, _weights, average_host, average_kept, upload
 
 EPS = 1e-5
 
@@ -271,10 +269,10 @@ def freq_host(data: Sequence[Sequence[np.ndarray]], weights=None) -> tuple:
             raise ValueError("client 0: FreqFed's feature is of layer [-2]; the upload has one layer")
         report = decide(gram_host([features_host(_matrix(x, i)) for i, x in enumerate(layers[-2])]), C)
     kept = report["kept"]
-    return [combine_host([xs[i] for i in kept], [w[i] for i in kept]) for xs in layers], report
+    return [average_host([xs[i] for i in kept], [w[i] for i in kept]) for xs in layers], report
 
 
-class FreqAggregator(FlameAggregator):
+class FreqAggregator(RobustAggregator):
     """FreqFed aggregator (frequency-domain Byzantine-robust aggregation).
 
     The computation is performed in plaintext.  ``average`` over the parties
@@ -284,7 +282,7 @@ class FreqAggregator(FlameAggregator):
     pinned memory) by ``sa_freq_features`` and ``sa_freq_gram``, read back in
     one pinned read, and the kept clients are averaged there: a list of
     float64 tensors on the device.  Uploads that are all host arrays run the
-    numpy form and give float64 arrays.  ``sum`` is ``FlameAggregator.sum``
+    numpy form and give float64 arrays.  ``sum`` is ``RobustAggregator.sum``
     (the reference inherits ``PlainAggregator.sum``).
 
     After each ``average``, ``last_report`` holds ``labels`` (a cluster number
@@ -296,9 +294,6 @@ class FreqAggregator(FlameAggregator):
       >>> aggregator = FreqAggregator(server)
       >>> fl = FLModel(server=server, device_list=clients, model=build, aggregator=aggregator)
     """
-
-    def __init__(self, device: PYU):
-        super().__init__(device)
 
     def _device_gram(self, rows: list, shape: tuple, dev) -> tuple:
         """The packed Gram matrix of the clients' features and whether the host computed it."""
@@ -337,29 +332,11 @@ class FreqAggregator(FlameAggregator):
         return average_kept(layers, on_dev, w, [i in report["kept"] for i in range(C)], dev)
 
     def _average(self, parties: list, weights):
-        single = not isinstance(parties[0], (list, tuple))
-        data = [[p] if single else list(p) for p in parties]
-        data = [[x if isinstance(x, torch.Tensor) else np.asarray(x) for x in d] for d in data]
-        for i, d in enumerate(data):
-            for l, x in enumerate(d):
-                if type(x).__name__ == "SparseCOO" or x.dtype == object:
-                    raise ValueError(f"layer {l}, client {i}: FreqAggregator takes dense float layers (sparse "
-                                     f"uploads: SparsePlainAggregator)")
-        w = _weights(weights, len(data))
-        layers = _layers(data)
-        _one_type(layers)
-        dev = next((x.device for xs in layers for x in xs if isinstance(x, torch.Tensor) and x.is_cuda), None)
+        single, data, layers, w, dev = self._parse(parties, weights, one_type=True)
         if dev is not None:
             outs = self._device_average(layers, w, weights is not None, dev)
         else:
-            host = [[x.detach().numpy() if isinstance(x, torch.Tensor) else x for x in d] for d in data]
-            outs, self.last_report = freq_host(host, None if weights is None else w)
+            outs, self.last_report = freq_host([[_host(x) for x in d] for d in data], None if weights is None else w)
         log.info("Nets for aggregation (no backdoor): %s; clusters: %s", self.last_report["kept"],
                  self.last_report["labels"])
         return outs[0] if single else outs
-
-    def average(self, data, axis=None, weights=None):
-        """The robust average over the parties (the module's definition)."""
-        if axis not in (None, 0):
-            raise ValueError(f"FreqAggregator aggregates over the parties (axis 0 or None), not axis {axis}")
-        return super().average(data, axis=axis, weights=weights)

@@ -88,7 +88,7 @@ import numpy as np
 import torch
 
 from ...device import PYU
-from .flame_aggregator import MAX_DEVICE_CLIENTS, FlameAggregator, _layers, _np_dtype, _weights
+from .robust import RobustAggregator, _host, _layers, _one_type, _weights, average_host, average_kept, upload
 
 MAX_P = 32  # SA_MARS_MAX_P: the Gram matrix of the smaller side lives in one wave's LDS
 WIDE_MAX_P = 512  # SA_MARS_WIDE_MAX_P: the Gram matrix in scratch, one block a matrix
@@ -205,18 +205,6 @@ def decide(features: Sequence[Sequence[np.ndarray]], plan: list, threshold: floa
 
 
 # ------------------------------------------------------------------ the whole
-def combine_host(xs: Sequence[np.ndarray], w: Sequence[float]) -> np.ndarray:
-    """Step 4 for one layer over the kept clients' arrays."""
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.average(xs, axis=0, weights=w) + 0.0
-
-
-def _one_type(layers: list) -> None:
-    for l, xs in enumerate(layers):
-        if _np_dtype(xs[0]) != _np_dtype(layers[0][0]):
-            raise ValueError(f"layer {l}, client 0: type {xs[0].dtype} differs from layer 0's {layers[0][0].dtype}")
-
-
 def mars_host(data: Sequence[Sequence[np.ndarray]], weights=None, threshold: float = 1.0) -> tuple:
     """The whole definition on host arrays: ``data[i][l]`` is client ``i``'s
     layer ``l``.  Returns (the float64 layers, the report)."""
@@ -231,57 +219,10 @@ def mars_host(data: Sequence[Sequence[np.ndarray]], weights=None, threshold: flo
     kept = [i for i in range(C) if report["labels"][i] == 0]
     if not kept:
         return [x.copy() for x in data[0]], report
-    return [combine_host([xs[i] for i in kept], [w[i] for i in kept]) for xs in layers], report
+    return [average_host([xs[i] for i in kept], [w[i] for i in kept]) for xs in layers], report
 
 
-def upload(layers: list, dev, who: str) -> list:
-    """``layers[l][i]`` as flat contiguous tensors on ``dev``: at most 16
-    clients; a host layer among device ones goes there through pinned memory."""
-    from ... import hostpipe as H
-
-    C = len(layers[0])
-    if C > MAX_DEVICE_CLIENTS:
-        raise NotImplementedError(f"{who} takes at most {MAX_DEVICE_CLIENTS} clients on the device "
-                                  f"(SA_FLAME_MAX_CLIENTS), got {C}; the host form takes any number")
-    on_dev = []
-    for l, xs in enumerate(layers):
-        row = []
-        for i, x in enumerate(xs):
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                if x.device != dev:
-                    raise ValueError(f"layer {l}, client {i}: on {x.device}, the others on {dev}")
-                row.append(x.detach().contiguous().reshape(-1))
-            else:  # a host layer among device ones: through pinned memory
-                row.append(H.h2d(x, dev).reshape(-1))
-        on_dev.append(row)
-    return on_dev
-
-
-def average_kept(layers: list, on_dev: list, w: List[float], keep: List[bool], dev) -> list:
-    """Step 4 on the device over ``upload``'s tensors: float64 layers in the uploads' shapes."""
-    from ... import hostpipe as H
-    from ... import kernels as K
-
-    C = len(layers[0])
-    kept_w = [w[i] for i in range(C) if keep[i]]
-    W = float(np.asarray(kept_w, np.float64).sum())
-    if W == 0.0:
-        raise ZeroDivisionError("Weights sum to zero, can't be normalized")
-    zero = torch.zeros(max(row[0].numel() for row in on_dev), dtype=on_dev[0][0].dtype, device=dev)
-    outs = []
-    for xs, row in zip(layers, on_dev):
-        n = row[0].numel()
-        if n <= 1:  # np.average itself (flame_aggregator's step 4), on a copy of at most one element
-            host = combine_host([H.d2h(row[i], pooled=False) for i in range(C) if keep[i]], kept_w)
-            outs.append(H.h2d(host, dev).reshape(tuple(xs[0].shape)))
-            continue
-        out = torch.empty(n, dtype=torch.float64, device=dev)
-        K.flame_combine(row, [1.0] * C, w, keep, zero[:n], W, out)
-        outs.append(out.reshape(tuple(xs[0].shape)))
-    return outs
-
-
-class MarsAggregator(FlameAggregator):
+class MarsAggregator(RobustAggregator):
     """MARS aggregator (Lipschitz-based Byzantine-robust aggregation).
 
     The computation is performed in plaintext.  ``average`` over the parties
@@ -291,7 +232,7 @@ class MarsAggregator(FlameAggregator):
     ``sa_mars_bn``, read back in one pinned read, and the kept clients are
     averaged there: a list of float64 tensors on the device.  Uploads that are
     all host arrays run the numpy form and give float64 arrays.  ``sum`` is
-    ``FlameAggregator.sum`` (the reference inherits ``PlainAggregator.sum``).
+    ``RobustAggregator.sum`` (the reference inherits ``PlainAggregator.sum``).
 
     After each ``average``, ``last_report`` holds ``labels`` (0 kept, -1 left
     out), ``features`` (every client's kept Lipschitz constants),
@@ -381,28 +322,10 @@ class MarsAggregator(FlameAggregator):
         return average_kept(layers, on_dev, w, keep, dev)
 
     def _average(self, parties: list, weights):
-        single = not isinstance(parties[0], (list, tuple))
-        data = [[p] if single else list(p) for p in parties]
-        data = [[x if isinstance(x, torch.Tensor) else np.asarray(x) for x in d] for d in data]
-        for i, d in enumerate(data):
-            for l, x in enumerate(d):
-                if type(x).__name__ == "SparseCOO" or x.dtype == object:
-                    raise ValueError(f"layer {l}, client {i}: MarsAggregator takes dense float layers (sparse "
-                                     f"uploads: SparsePlainAggregator)")
-        w = _weights(weights, len(data))
-        layers = _layers(data)
-        _one_type(layers)
-        dev = next((x.device for xs in layers for x in xs if isinstance(x, torch.Tensor) and x.is_cuda), None)
+        single, data, layers, w, dev = self._parse(parties, weights, one_type=True)
         if dev is not None:
             outs = self._device_average(layers, w, dev)
         else:
-            host = [[x.detach().numpy() if isinstance(x, torch.Tensor) else x for x in d] for d in data]
-            outs, self.last_report = mars_host(host, w, self.anomaly_threshold)
+            outs, self.last_report = mars_host([[_host(x) for x in d] for d in data], w, self.anomaly_threshold)
         log.info("Anomaly detection results: %s", self.last_report["labels"])
         return outs[0] if single else outs
-
-    def average(self, data, axis=None, weights=None):
-        """The robust average over the parties (the module's definition)."""
-        if axis not in (None, 0):
-            raise ValueError(f"MarsAggregator aggregates over the parties (axis 0 or None), not axis {axis}")
-        return super().average(data, axis=axis, weights=weights)

@@ -106,3 +106,38 @@ def test_a_refused_scratch_size_falls_back_to_the_host(monkeypatch):
     out = agg.average(uploads, axis=0, weights=weights).data
     assert agg.last_report["host_fallback"] == 1 and agg.last_report["kept"] == O.KEPT
     assert all(np.array_equal(gpu_copies._host(o), w) for o, w in zip(out, F.freq_host(data, weights)[0]))
+
+
+def test_the_upload_takes_a_host_layer_and_refuses_a_second_device():
+    """Six clients of three small layers, four of them near one model: client 2 uploads a numpy layer [-2]
+    among device tensors, and where a second device is visible client 4's layer 0 arrives from it
+    (``average`` moves it to the server's)."""
+    from sfl_amd.device import PYU, PYUObject
+    from sfl_amd.security.aggregation import FreqAggregator
+    from sfl_amd.security.aggregation.robust import upload
+
+    dev, two = _dev(), torch.cuda.device_count() >= 2
+    rng = np.random.default_rng(11)
+    shapes = ((8,), (8, 8), (8,))
+    base = [rng.standard_normal(s) for s in shapes]
+    data = [[((b if i < 4 else rng.standard_normal(b.shape)) + 0.01 * rng.standard_normal(b.shape)).astype(np.float32)
+             for b in base] for i in range(6)]
+    weights, server = [1, 2, 3, 4, 5, 6], PYU("server", 0)
+
+    def place(i, l, a):
+        if (i, l) == (2, 1):
+            return a
+        return gpu_copies._dev(a, device="cuda:1" if two and (i, l) == (4, 0) else gpu_copies.DEV).reshape(a.shape)
+
+    uploads = [PYUObject(server, [place(i, l, a) for l, a in enumerate(d)]) for i, d in enumerate(data)]
+    agg = FreqAggregator(server)
+    out = agg.average(uploads, axis=0, weights=weights).data
+    want, host = F.freq_host(data, weights)
+    assert agg.last_report["labels"] == host["labels"] and agg.last_report["kept"] == host["kept"] == [0, 1, 2, 3]
+    for o, w in zip(out, want):
+        assert o.device == dev and o.dtype == torch.float64 and o.shape == w.shape
+        assert np.array_equal(gpu_copies._host(o), w)  # bit for bit
+    if two:  # past ``average``'s move, a layer on another device is refused where it is found
+        layers = [[u.data[l] for u in uploads] for l in range(3)]
+        with pytest.raises(ValueError, match="layer 0, client 4: on cuda:1, the others on cuda:0"):
+            upload(layers, dev, "FreqAggregator")

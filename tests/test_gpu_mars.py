@@ -156,3 +156,35 @@ def test_seventeen_clients_on_the_device_are_refused():
     data = [PYUObject(server, [torch.ones(8, device=dev) * i]) for i in range(17)]
     with pytest.raises(NotImplementedError, match="16"):
         MarsAggregator(server).average(data, axis=0)
+
+
+def test_the_upload_takes_a_host_layer_and_refuses_a_second_device():
+    """Six clients of three small layers: client 2 uploads a numpy layer among device tensors, and where a
+    second device is visible client 4's layer 0 arrives from it (``average`` moves it to the server's).  The
+    threshold keeps every client: the decisions are the planted case's subject, the upload is this one's."""
+    from sfl_amd.device import PYU, PYUObject
+    from sfl_amd.security.aggregation import MarsAggregator
+    from sfl_amd.security.aggregation.robust import upload
+
+    dev, two = _dev(), torch.cuda.device_count() >= 2
+    rng = np.random.default_rng(7)
+    data = [[rng.standard_normal(s).astype(np.float32) for s in ((8, 8), (8,), (4, 8))] for _ in range(6)]
+    weights, server = [1, 2, 3, 4, 5, 6], PYU("server", 0)
+
+    def place(i, l, a):
+        if (i, l) == (2, 1):
+            return a
+        return gpu_copies._dev(a, device="cuda:1" if two and (i, l) == (4, 0) else gpu_copies.DEV).reshape(a.shape)
+
+    uploads = [PYUObject(server, [place(i, l, a) for l, a in enumerate(d)]) for i, d in enumerate(data)]
+    agg = MarsAggregator(server, anomaly_threshold=1e300)
+    out = agg.average(uploads, axis=0, weights=weights).data
+    want, host = M.mars_host(data, weights, 1e300)
+    assert agg.last_report["labels"] == host["labels"] == [0] * 6 and agg.last_report["host_layers"] == 0
+    for o, w in zip(out, want):
+        assert o.device == dev and o.dtype == torch.float64 and o.shape == w.shape
+        assert np.array_equal(gpu_copies._host(o), w)  # bit for bit
+    if two:  # past ``average``'s move, a layer on another device is refused where it is found
+        layers = [[u.data[l] for u in uploads] for l in range(3)]
+        with pytest.raises(ValueError, match="layer 0, client 4: on cuda:1, the others on cuda:0"):
+            upload(layers, dev, "MarsAggregator")
